@@ -9,6 +9,12 @@ xGMI (torch.distributed backend "nccl" on ROCm).
 Usage (driver contract):
   python bench.py --gpus N --steps K --warmup W
   torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result
+line.  --dump-outputs DIR additionally writes what the last timed step
+produced (the new tree and the updated training margin) as DIR/<name>.npy;
+inputs are seeded, so two builds can be compared output for output.
+--full adds the checks that need passes of their own (training AUC).
 """
 import argparse
 import json
@@ -35,6 +41,26 @@ def make_higgs_like(n_rows: int, n_features: int = 28, seed: int = 0):
     return X.numpy().astype(np.float32), y.numpy().astype(np.float32)
 
 
+# per-node arrays of a grown tree, as RegTree holds them
+_TREE_FIELDS = ("left", "right", "split_index", "split_cond", "default_left",
+                "loss_chg", "sum_hess", "base_weight")
+
+
+def dump_outputs(out_dir: str, bst, dtrain) -> None:
+    """Write the results of the last boosting step as float32 .npy files:
+    the tree that step appended and the training margin it updated (the
+    booster's prediction cache for dtrain, which the next step's gradients
+    are taken from).  1M rows -> ~4 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    tree = bst.trees[-1]
+    for name in _TREE_FIELDS:
+        arr = np.asarray(getattr(tree, name)[:tree.n_nodes], dtype=np.float32)
+        np.save(os.path.join(out_dir, f"tree_{name}.npy"), arr)
+    margin = bst._cached_margin(dtrain).detach().cpu().numpy()
+    np.save(os.path.join(out_dir, "margin.npy"),
+            np.asarray(margin, dtype=np.float32).reshape(-1))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -44,7 +70,14 @@ def main() -> None:
     ap.add_argument("--features", type=int, default=28)
     ap.add_argument("--max-depth", type=int, default=8)
     ap.add_argument("--max-bin", type=int, default=256)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks outside the headline figure "
+                         "(training AUC)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -92,10 +125,15 @@ def main() -> None:
     if collective.is_distributed():
         elapsed = collective.allreduce_max_scalars([elapsed])[0]
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bst, dtrain)
+
     # correctness: AUC on the training shard (outside timed region)
-    from xgboost_amd.metrics import create_metric
-    pred = bst.predict(dtrain)
-    auc = create_metric("auc")(pred, dtrain.info)
+    auc = None
+    if args.full:
+        from xgboost_amd.metrics import create_metric
+        pred = bst.predict(dtrain)
+        auc = round(float(create_metric("auc")(pred, dtrain.info)), 5)
 
     value = args.steps / elapsed
     if rank == 0:
@@ -120,7 +158,7 @@ def main() -> None:
                 "max_bin": args.max_bin,
                 "objective": "binary:logistic",
                 "parallelism": f"dp{world_size}",
-                "train_auc": round(float(auc), 5),
+                "train_auc": auc,
                 "device": params["device"],
             },
         }

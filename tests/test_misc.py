@@ -490,3 +490,41 @@ def test_gpu_id_deprecated_spelling():
     assert str(b.device) == "cuda:1"
     b2 = xgb.Booster({"device": "cpu", "gpu_id": 0})
     assert b2.device.type == "cpu"  # explicit device wins
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """bench.py --dump-outputs writes the last step's tree and margin as
+    float arrays; --full adds the training-AUC check a plain run skips."""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rows = 5000
+
+    def run(*extra):
+        out = subprocess.run(
+            [sys.executable, os.path.join(repo, "bench.py"), "--steps", "2",
+             "--warmup", "1", "--rows", str(rows), *extra],
+            capture_output=True, text=True, timeout=300, cwd=repo)
+        assert out.returncode == 0, out.stdout + out.stderr
+        return json.loads(out.stdout.strip().splitlines()[-1])
+
+    plain = run("--dump-outputs", str(tmp_path / "a"))
+    full = run("--full", "--dump-outputs", str(tmp_path / "b"))
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0
+    assert plain["config"]["train_auc"] is None
+    assert 0.5 < full["config"]["train_auc"] <= 1.0
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert "margin.npy" in names and "tree_split_cond.npy" in names
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    total = 0
+    for name in names:
+        a = np.load(tmp_path / "a" / name)
+        b = np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64), name
+        # seeded inputs: two runs give the same outputs
+        np.testing.assert_array_equal(a, b, err_msg=name)
+        total += a.nbytes
+    assert np.load(tmp_path / "a" / "margin.npy").shape == (rows,)
+    assert total <= 64 * 2 ** 20
