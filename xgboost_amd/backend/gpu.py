@@ -1072,3 +1072,205 @@ def predict_margin_gpu(booster, dmat, out_margin: torch.Tensor,
         out_margin.shape[1], hip_ops.ptr(out_margin), hip_ops.ptr(out_leaf),
         hip_ops.stream())
     return out_margin
+
+
+# ---------------------------------------------------------------------------
+# packed-node predictor (predict_bins.hip): quantized pages, raw floats,
+# vector leaves, leaf indices
+
+_DEFAULT_LEFT_BIT = np.uint32(1 << 31)
+_IS_CAT_BIT = np.uint32(1 << 30)
+
+
+class _ForestQ:
+    """Device forest for gbt_predict_q: one 16-byte record per node
+    {left, right, feature | default_left<<31 | is_cat<<30, value}.  The
+    value word is the leaf value at a leaf and otherwise the LOCAL split
+    bin against `cuts` (bins kinds) or the split_cond bits (cuts=None,
+    raw floats).  Vector-leaf trees get tree_group -1 and their rows in
+    leaf_vec; DART tree weights are folded into both leaf stores."""
+
+    def __init__(self, booster, idxs, device, cuts=None):
+        from ..tree_model import local_split_bins
+        idxs = list(idxs)
+        trees = [booster.trees[i] for i in idxs]
+        K = int(booster.n_outputs)
+        offs = np.zeros(len(trees) + 1, np.int32)
+        for i, t in enumerate(trees):
+            offs[i + 1] = offs[i] + t.n_nodes
+        total = int(offs[-1])
+        nodes = np.zeros((total, 4), np.uint32)
+        cat_off = np.zeros(total + 1, np.int32)
+        cat_bits: List[np.ndarray] = []
+        group = np.empty(len(trees), np.int32)
+        vec_off = np.zeros(len(trees), np.int32)
+        vecs: List[np.ndarray] = []
+        n_vec = 0
+        for i, t in enumerate(trees):
+            n = t.n_nodes
+            o = int(offs[i])
+            left = t.left[:n]
+            leaf = left == -1
+            w = np.float32(booster._tw(idxs[i]))
+            rec = nodes[o:o + n]
+            rec[:, 0] = left.view(np.uint32)
+            rec[:, 1] = t.right[:n].view(np.uint32)
+            feat = t.split_index[:n].astype(np.uint32)
+            feat[leaf] = 0
+            rec[:, 2] = (feat
+                         | np.where(t.default_left[:n] != 0,
+                                    _DEFAULT_LEFT_BIT, np.uint32(0))
+                         | np.where(t.split_type[:n] == 1,
+                                    _IS_CAT_BIT, np.uint32(0)))
+            cond = t.split_cond[:n].astype(np.float32)
+            val = cond.view(np.uint32).copy()
+            if cuts is not None:
+                inner = ~leaf
+                val[inner] = local_split_bins(
+                    t.split_index[:n][inner], cond[inner],
+                    cuts).view(np.uint32)
+            if t.leaf_values is not None:
+                group[i] = -1
+                vec_off[i] = n_vec
+                lv = t.leaf_values[:n].astype(np.float32).reshape(n, K)
+                vecs.append(lv * w if w != 1.0 else lv)
+                n_vec += n
+                val[leaf] = 0
+            else:
+                group[i] = booster.tree_info[idxs[i]]
+                if w != 1.0:
+                    val[leaf] = (cond[leaf] * w).view(np.uint32)
+            rec[:, 3] = val
+            nw_node = np.zeros(n, np.int64)
+            for nid in sorted(t.cat_segments):
+                if nid < n and t.split_type[nid] == 1:
+                    cats = t.cat_segments[nid]
+                    nw = (int(cats.max()) >> 5) + 1 if len(cats) else 0
+                    bits = np.zeros(nw, np.uint32)
+                    np.bitwise_or.at(
+                        bits, np.asarray(cats, np.int64) >> 5,
+                        np.uint32(1) << (np.asarray(cats, np.uint32)
+                                         & np.uint32(31)))
+                    cat_bits.append(bits)
+                    nw_node[nid] = nw
+            prev = int(cat_off[o])
+            cat_off[o + 1:o + n + 1] = prev + np.cumsum(nw_node)
+        self.cuts = cuts
+        self.n_trees = len(trees)
+        self.n_outputs = K
+        self.nodes = torch.from_numpy(nodes.view(np.int32)).to(device)
+        self.tree_offsets = torch.from_numpy(offs).to(device)
+        self.cat_offsets = torch.from_numpy(cat_off).to(device)
+        if cat_bits:
+            self.cat_bits = torch.from_numpy(
+                np.concatenate(cat_bits).view(np.int32)).to(device)
+        else:
+            self.cat_bits = torch.zeros(1, dtype=torch.int32, device=device)
+        self.tree_group = torch.from_numpy(group).to(device)
+        self.vec_offset = torch.from_numpy(vec_off).to(device)
+        if vecs:
+            self.leaf_vec = torch.from_numpy(
+                np.ascontiguousarray(np.concatenate(vecs))).to(device)
+        else:
+            self.leaf_vec = torch.zeros(1, dtype=torch.float32,
+                                        device=device)
+        if cuts is not None:
+            self.n_bins = torch.from_numpy(
+                np.diff(cuts.ptrs).astype(np.int32)).to(device)
+        else:
+            self.n_bins = None
+
+
+def _cached_forest_q(booster, lo: int, hi: int, device, cuts) -> _ForestQ:
+    """_ForestQ for trees [lo, hi) cached across predict calls, keyed by
+    the model state AND the cuts object the split bins were built for
+    (None = raw floats).  Entries of an older model state are dropped."""
+    wd = getattr(booster, "weight_drop", None)
+    state = (len(booster.trees), str(device),
+             None if not wd else tuple(wd))
+    fc = booster.__dict__.setdefault("_forest_q_cache", {})
+    for k in [k for k in fc if k[0] != state]:
+        del fc[k]
+    key = (state, lo, hi, None if cuts is None else id(cuts))
+    fa = fc.get(key)
+    if fa is None or fa.cuts is not cuts:
+        if len(fc) >= 8:  # iteration_range sweeps: keep the cache small
+            fc.clear()
+        fa = _ForestQ(booster, range(lo, hi), device, cuts)
+        fc[key] = fa
+    return fa
+
+
+_Q_KIND = {torch.float32: 0, torch.uint8: 1, torch.int16: 2}
+
+
+def _launch_predict_q(fa: _ForestQ, X: torch.Tensor, missing: float,
+                      out: Optional[torch.Tensor],
+                      out_leaf: Optional[torch.Tensor]) -> None:
+    from .. import ops as hip_ops
+    lib = hip_ops.load()
+    kind = _Q_KIND[X.dtype]
+    if kind != 0 and fa.n_bins is None:
+        raise ValueError("bin input needs a forest built against its cuts")
+    n, F = X.shape
+    assert out is None or (out.is_contiguous() and out.shape[0] == n
+                           and out.shape[1] == fa.n_outputs)
+    assert out_leaf is None or (out_leaf.is_contiguous()
+                                and out_leaf.dtype == torch.int32
+                                and out_leaf.shape == (n, fa.n_trees))
+    missing_is_nan = 1 if np.isnan(missing) else 0
+    lib.gbt_predict_q(
+        hip_ops.ptr(X), kind, n, F,
+        float(0.0 if missing_is_nan else missing), missing_is_nan,
+        hip_ops.ptr(fa.n_bins), hip_ops.ptr(fa.nodes),
+        hip_ops.ptr(fa.tree_offsets), hip_ops.ptr(fa.cat_offsets),
+        hip_ops.ptr(fa.cat_bits), hip_ops.ptr(fa.tree_group),
+        hip_ops.ptr(fa.vec_offset), hip_ops.ptr(fa.leaf_vec), fa.n_trees,
+        fa.n_outputs, hip_ops.ptr(out), hip_ops.ptr(out_leaf),
+        hip_ops.stream())
+
+
+def predict_q_supported(dmat) -> bool:
+    """True when gbt_predict_q can read `dmat`: dense raw floats, or
+    external-memory pages stored as u8/u16 local bins."""
+    from ..extmem import ExtMemQuantileDMatrix
+    if isinstance(dmat, ExtMemQuantileDMatrix):
+        # disk-spilled pages keep their dtype on the placeholder
+        return all(qm.gidx.dtype in (torch.uint8, torch.int16)
+                   for qm in dmat.pages)
+    return getattr(dmat, "_sparse_data", None) is None
+
+
+def predict_margin_q_gpu(booster, dmat, out: Optional[torch.Tensor],
+                         lo: int, hi: int, idxs=None,
+                         out_leaf: Optional[torch.Tensor] = None):
+    """Add trees [lo, hi) (or the DART subset `idxs`, never cached) to
+    `out` [n, n_outputs] and/or write leaf ids to `out_leaf` [n, n_trees]
+    int32.  External-memory matrices are read page by page as stored
+    (u8/u16 local bins); other matrices as dense raw floats."""
+    from ..extmem import ExtMemQuantileDMatrix
+    device = out.device if out is not None else out_leaf.device
+    extmem = isinstance(dmat, ExtMemQuantileDMatrix)
+    cuts = dmat.cuts if extmem else None
+    if idxs is not None:
+        fa = _ForestQ(booster, idxs, device, cuts)
+    else:
+        fa = _cached_forest_q(booster, lo, hi, device, cuts)
+    if fa.n_trees == 0:
+        return out
+    if not extmem:
+        dd = dmat.device_data() if hasattr(dmat, "device_data") else None
+        X = dd if dd is not None else \
+            torch.from_numpy(dmat.raw_data()).to(device)
+        _launch_predict_q(fa, X.contiguous(), dmat.missing, out, out_leaf)
+        return out
+    for pi in range(len(dmat.pages)):
+        s, e = dmat.page_offsets[pi], dmat.page_offsets[pi + 1]
+        if e == s:
+            continue
+        # upload on the current stream: ordered before the launch
+        gidx = dmat.page_qm(pi).gidx.to(device)
+        _launch_predict_q(fa, gidx.contiguous(), float("nan"),
+                          None if out is None else out[s:e],
+                          None if out_leaf is None else out_leaf[s:e])
+    return out

@@ -354,6 +354,13 @@ class Booster:
         if isinstance(dmat, ExtMemQuantileDMatrix):
             # quantized-only pages: bin-based traversal per page (the
             # split conds are cut values, so this is exact)
+            if self.device.type == "cuda":
+                from .backend.gpu import (predict_margin_q_gpu,
+                                          predict_q_supported)
+                if predict_q_supported(dmat):
+                    return predict_margin_q_gpu(self, dmat, out, 0, 0,
+                                                idxs=list(idxs))
+            # host walk: CPU boosters and int32-bin pages
             for pi in range(len(dmat.pages)):
                 qm = dmat.page_qm(pi)
                 s, e = dmat.page_offsets[pi], dmat.page_offsets[pi + 1]
@@ -361,6 +368,11 @@ class Booster:
                 for t in idxs:
                     tree = self.trees[t]
                     pos = tree.predict_leaf_bins(gg, dmat.cuts)
+                    if tree.leaf_values is not None:  # vector leaves
+                        out[s:e] += self._tw(t) * torch.as_tensor(
+                            tree.leaf_values[:tree.n_nodes][pos],
+                            device=out.device)
+                        continue
                     vals = tree.split_cond[:tree.n_nodes][pos] * self._tw(t)
                     out[s:e, self.tree_info[t]] += torch.as_tensor(
                         vals, device=out.device)
@@ -932,6 +944,7 @@ class Booster:
                                  device=self.device)
             out = bm.view(n, -1).expand(n, self.n_outputs).clone()
         if self.booster_kind == "gblinear":
+            # linear model: one dense matmul in torch, no trees to walk
             if self._linear is not None:
                 X = torch.as_tensor(dmat.raw_data(), device=self.device)
                 out = out + self._linear.predict_margin(X)
@@ -941,6 +954,7 @@ class Booster:
         if isinstance(dmat, ExtMemQuantileDMatrix):
             return self._predict_margin_extmem(dmat, out, lo, hi)
         if getattr(dmat, "_sparse_data", None) is not None:
+            # sparse CSR stays on the host (no CSR predict kernel)
             return self._predict_margin_sparse(dmat, out, lo, hi)
         train_cats = getattr(self, "cat_categories_", None)
         pred_cats = getattr(dmat, "categories_", None)
@@ -953,11 +967,15 @@ class Booster:
             X = align_categories(dmat.raw_data(), pred_cats, train_cats)
             aligned = True
         has_mt = any(t.leaf_values is not None for t in self.trees[lo:hi])
-        if self.device.type == "cuda" and (hi - lo) > 0 and not has_mt \
-                and not aligned:
+        if self.device.type == "cuda" and (hi - lo) > 0 and not aligned:
             # device-resident inputs never round-trip to host here
+            if has_mt:  # vector leaves: packed-node kernel on raw floats
+                from .backend.gpu import predict_margin_q_gpu
+                return predict_margin_q_gpu(self, dmat, out, lo, hi)
             from .backend.gpu import predict_margin_gpu
             return predict_margin_gpu(self, dmat, out, lo, hi)
+        # host walk: CPU boosters and re-aligned categories (the recoded
+        # matrix exists only on the host)
         if X is None:
             X = dmat.raw_data()
         for t in range(lo, hi):
@@ -1016,6 +1034,12 @@ class Booster:
     def _predict_margin_extmem(self, dmat, out: torch.Tensor,
                                lo: int, hi: int) -> torch.Tensor:
         """Bin-based traversal per quantized page (no raw values)."""
+        if self.device.type == "cuda":
+            from .backend.gpu import (predict_margin_q_gpu,
+                                      predict_q_supported)
+            if predict_q_supported(dmat):
+                return predict_margin_q_gpu(self, dmat, out, lo, hi)
+        # host walk: CPU boosters and int32-bin pages (> 65535 local bins)
         for pi in range(len(dmat.pages)):
             qm = dmat.page_qm(pi)  # loads disk-spilled pages on demand
             s, e = dmat.page_offsets[pi], dmat.page_offsets[pi + 1]
@@ -1023,10 +1047,44 @@ class Booster:
             for t in range(lo, hi):
                 tree = self.trees[t]
                 pos = tree.predict_leaf_bins(gg, dmat.cuts)
+                if tree.leaf_values is not None:  # vector leaves
+                    out[s:e] += self._tw(t) * torch.as_tensor(
+                        tree.leaf_values[:tree.n_nodes][pos],
+                        device=out.device)
+                    continue
                 vals = tree.split_cond[:tree.n_nodes][pos]
                 out[s:e, self.tree_info[t]] += self._tw(t) * torch.as_tensor(
                     vals, device=out.device)
         return out
+
+    def _predict_leaf(self, data: DMatrix, lo: int, hi: int) -> np.ndarray:
+        """Leaf node id of every row in trees [lo, hi): int32 [n, hi-lo]."""
+        from .extmem import ExtMemQuantileDMatrix
+        extmem = isinstance(data, ExtMemQuantileDMatrix)
+        if self.device.type == "cuda" and hi > lo:
+            from .backend.gpu import predict_margin_q_gpu, predict_q_supported
+            train_cats = getattr(self, "cat_categories_", None)
+            pred_cats = getattr(data, "categories_", None)
+            aligned = bool(train_cats and pred_cats
+                           and pred_cats != train_cats)
+            if predict_q_supported(data) and not aligned:
+                leaf = torch.empty((data.num_row(), hi - lo),
+                                   dtype=torch.int32, device=self.device)
+                predict_margin_q_gpu(self, data, None, lo, hi, out_leaf=leaf)
+                return leaf.cpu().numpy()
+        # host walk: CPU boosters, sparse CSR, re-aligned categorical
+        # frames and int32-bin pages
+        if extmem:
+            pages = []
+            for pi in range(len(data.pages)):
+                gg = data.page_qm(pi).global_gidx().cpu().numpy()
+                pages.append(np.stack(
+                    [self.trees[t].predict_leaf_bins(gg, data.cuts)
+                     for t in range(lo, hi)], axis=1))
+            return np.concatenate(pages, axis=0)
+        X = data.raw_data()
+        return np.stack([self.trees[t].predict_leaf_np(X, data.missing)
+                         for t in range(lo, hi)], axis=1)
 
     def _tree_range(self, iteration_range: Tuple[int, int]) -> Tuple[int, int]:
         lo_it, hi_it = iteration_range
@@ -1064,10 +1122,7 @@ class Booster:
                    if given - trained else ""))
         if pred_leaf:
             lo, hi = self._tree_range(iteration_range)
-            X = data.raw_data()
-            out = np.stack([self.trees[t].predict_leaf_np(X, data.missing)
-                            for t in range(lo, hi)], axis=1)
-            out = out.astype(np.float32)
+            out = self._predict_leaf(data, lo, hi).astype(np.float32)
             if strict_shape:
                 # reference: (n, n_iterations, n_groups, n_parallel_tree)
                 npt = max(1, self.tparam.num_parallel_tree)

@@ -36,6 +36,8 @@ _SIGS = {
     "gbt_compress": [_p, _i64, _i, _p, _p, _p, _f, _i, _p, _p, _p],
     "gbt_predict": [_p, _i64, _i, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p,
                     _p, _p, _i, _i, _p, _p, _p],
+    "gbt_predict_q": [_p, _i, _i64, _i, _f, _i, _p, _p, _p, _p, _p, _p, _p,
+                      _p, _i, _i, _p, _p, _p],
     "gbt_leaf_partition": [_p, _p, _i, _p, _p, _p],
     "gbt_leaf_decide": [_p, _p, _i, _p, _p, _i64, _p, _p, _i, _p, _p, _p,
                         _p, _p, _p, _p],

@@ -9,7 +9,7 @@ SRC = os.path.join(HERE, "cpp")
 OUT = os.path.join(HERE, "libgbt_hip.so")
 
 SOURCES = ["hist.hip", "partition.hip", "evaluate.hip", "compress.hip",
-           "predict.hip", "shap.hip", "shap_paths.hip", "shap_ix.hip",
+           "predict.hip", "predict_bins.hip", "shap.hip", "shap_paths.hip", "shap_ix.hip",
            "driver.hip", "csr.hip", "gpair.hip", "mt_evaluate.hip",
            "cpu_hist.cpp"]
 

@@ -105,6 +105,27 @@ void gbt_predict(const float* X, int64_t n_rows, int n_features,
                  int32_t* out_leaf,            // [n_rows, n_trees] or null
                  hipStream_t stream);
 
+// Packed-node predictor (predict_bins.hip).  X is row-major [n, F] of
+// kind 0 = float raw values, 1 = uint8 local bins, 2 = uint16 local bins.
+// nodes: 16-byte records {left, right, feature | default_left<<31 |
+// is_cat<<30, split_bin (bins) or split_cond bits (raw); leaf value bits
+// at a leaf}.  tree_group[t] == -1 marks a vector-leaf tree whose leaf
+// nid adds leaf_vec[(vec_offset[t] + nid) * n_groups + k] to column k.
+void gbt_predict_q(const void* X, int kind, int64_t n_rows, int n_features,
+                   float missing_value, int missing_is_nan,
+                   const int32_t* n_bins,        // [n_features] (bins kinds)
+                   const void* nodes,            // [total_nodes] int4
+                   const int32_t* tree_offsets,  // [n_trees+1]
+                   const int32_t* cat_offsets,   // [total_nodes+1]
+                   const uint32_t* cat_bits,
+                   const int32_t* tree_group,    // [n_trees]
+                   const int32_t* vec_offset,    // [n_trees]
+                   const float* leaf_vec,        // [vec_nodes, n_groups]
+                   int n_trees, int n_groups,
+                   float* out_margin,            // [n_rows, n_groups] or null
+                   int32_t* out_leaf,            // [n_rows, n_trees] or null
+                   hipStream_t stream);
+
 void gbt_leaf_decide(const uint8_t* gidx8, const uint16_t* gidx16,
                      int n_features,
                      const uint8_t* gidx8_col, const uint16_t* gidx16_col,

@@ -17,6 +17,23 @@ import numpy as np
 _INIT_CAP = 8
 
 
+def local_split_bins(split_index: np.ndarray, split_cond: np.ndarray,
+                     cuts) -> np.ndarray:
+    """Per-node LOCAL split bin searchsorted(feature_cuts(f), cond,
+    side="left"), vectorised per feature: a row with local bin `b` at
+    that node goes left iff b <= split_bin (RegTree.predict_leaf_bins
+    uses the same rule on global ids).  Entries of leaf nodes are
+    computed too and are meaningless."""
+    split_index = np.asarray(split_index)
+    split_cond = np.asarray(split_cond, dtype=np.float32)
+    out = np.zeros(split_index.shape[0], dtype=np.int32)
+    for f in np.unique(split_index):
+        m = split_index == f
+        out[m] = np.searchsorted(cuts.feature_cuts(int(f)), split_cond[m],
+                                 side="left")
+    return out
+
+
 class RegTree:
     """Binary tree with scalar leaves (vector leaves: see n_targets>1)."""
 
