@@ -628,9 +628,10 @@ class GpuOps(SegmentedOpsMixin):
                 mp = n_rows // 1024 + pool + 2
                 # + 2 fp64 bound ping-pong buffers (monotone whole-tree)
                 # + per-level built-is-left mode records
+                # + the 24-byte root sums / max-abs readback slot
                 wt_bytes = (48 * rec + 8 * rec + 8 * (param.max_depth + 2)
                             + 96 * pool + 32 * pool + 16 * mp
-                            + param.max_depth * pool + 32 * 1024)
+                            + param.max_depth * pool + 24 + 32 * 1024)
                 ws["wt_max_ptasks"] = mp
                 ws["wt_ws"] = torch.empty(wt_bytes, dtype=torch.uint8,
                                           device=dev)

@@ -58,6 +58,7 @@ _SIGS = {
     # native level-loop driver
     "gbt_driver_create": [],
     "gbt_driver_destroy": [_p],
+    "gbt_root_tasks_check": [_i64, _i64, _i64, _p],
     "gbt_grow_tree": [
         _p,                      # ctx
         _p, _p, _i,              # gidx8/16, n_features
@@ -118,6 +119,8 @@ def load() -> ctypes.CDLL:
     if hasattr(_lib, "gbt_driver_create"):
         _lib.gbt_driver_create.restype = _p
         _lib.gbt_grow_tree.restype = _c.c_int
+    if hasattr(_lib, "gbt_root_tasks_check"):
+        _lib.gbt_root_tasks_check.restype = _c.c_int
     if hasattr(_lib, "gbt_partition_cpu"):
         _lib.gbt_partition_cpu.restype = _c.c_longlong
     return _lib

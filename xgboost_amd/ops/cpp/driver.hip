@@ -73,10 +73,8 @@ struct DriverCtx {
   // sequence is identical every round (no host decisions mid-chain), so
   // after one capture the ~25 launches/tree replay as ONE graph launch.
   // Valid only while every baked address is unchanged — wt_key records
-  // them all and any mismatch forces a recapture.  The chain's host
-  // staging lives in a DEDICATED pinned buffer (not the rotating ring)
-  // so the baked source addresses stay stable; its contents are
-  // rewritten before every launch (replays read them at execution).
+  // them all and any mismatch forces a recapture.  The chain needs no
+  // host staging: its per-tree constants are written by its init kernel.
   hipGraphExec_t wt_graph = nullptr;
   std::vector<unsigned long long> wt_key;
   // capture-on-second-sight: a key must repeat once before we pay the
@@ -84,9 +82,6 @@ struct DriverCtx {
   // approx path rebuilds its ops every iteration — would otherwise
   // capture every round and never replay)
   std::vector<unsigned long long> wt_seen_key;
-  void* wtc_host = nullptr;
-  void* wtc_dev = nullptr;
-  size_t wtc_cap = 0;
   // capture needs a REAL stream: the caller usually passes torch's
   // default stream (0), and capturing a null-stream alias leaves the
   // legacy stream wedged in capture state.  The chain runs on this
@@ -111,17 +106,6 @@ struct DriverCtx {
     readback_cap = want;
     return 0;
   }
-  int ensure_const(size_t bytes) {
-    if (wtc_cap >= bytes) return 0;
-    size_t want = 4096;
-    while (want < bytes) want <<= 1;
-    if (wtc_host) hipHostFree(wtc_host);
-    if (wtc_dev) hipFree(wtc_dev);
-    HIP_CHECK(hipHostMalloc(&wtc_host, want));
-    HIP_CHECK(hipMalloc(&wtc_dev, want));
-    wtc_cap = want;
-    return 0;
-  }
   ~DriverCtx() {
     for (int i = 0; i < PinnedRing::kSlots; ++i) {
       if (ring.host[i]) hipHostFree(ring.host[i]);
@@ -129,8 +113,6 @@ struct DriverCtx {
     }
     if (readback_host) hipHostFree(readback_host);
     if (wt_graph) (void)hipGraphExecDestroy(wt_graph);
-    if (wtc_host) hipHostFree(wtc_host);
-    if (wtc_dev) hipFree(wtc_dev);
     if (gstream) (void)hipStreamDestroy(gstream);
     if (gevent) (void)hipEventDestroy(gevent);
   }
@@ -228,6 +210,52 @@ __global__ void ZeroI64Kernel(int64_t* p, long long n) {
 __global__ void IotaKernel(int32_t* r, long long n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i < n; i += (long long)gridDim.x * blockDim.x) r[i] = (int)i;
+}
+
+// root hist tasks of a [0, n_rows) segment: same layout as ChunkTasks
+// over the single root node
+long long RootRowsPerTask(long long n_rows, long long min_rows,
+                          long long target_tasks) {
+  return std::max<long long>(min_rows,
+                             (n_rows + target_tasks - 1) / target_tasks);
+}
+int RootTaskCount(long long n_rows, long long rpt) {
+  return (int)std::max<long long>(1, (n_rows + rpt - 1) / rpt);
+}
+
+// Whole-tree chain head: row-id iota + root-histogram zero + every
+// per-tree constant the chain used to stage from the host (they depend
+// only on the configuration): kn=1, kp=0, the root segment, the root
+// hist task list.  Block 0 also copies the root sums and gradient
+// max-abs into the readback span so ONE D2H copy returns everything.
+__global__ void WtInitKernel(int32_t* r, long long n, int64_t* zero,
+                             long long zero_n, int32_t* kn, int32_t* kp,
+                             int32_t* seg, BlockTask* root_tasks,
+                             int n_root_tasks, long long rpt,
+                             const int64_t* __restrict__ root_sums,
+                             const float* __restrict__ maxabs,
+                             int64_t* rs_out /* [2] sums + 2 floats */) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long long i = i0; i < n; i += stride) r[i] = (int)i;
+  for (long long i = i0; i < zero_n; i += stride) zero[i] = 0;
+  if (blockIdx.x != 0) return;
+  if (threadIdx.x == 0) {
+    kn[0] = 1;
+    kp[0] = 0;
+    seg[0] = 0;
+    seg[1] = (int)n;
+    rs_out[0] = root_sums[0];
+    rs_out[1] = root_sums[1];
+    float* ma = (float*)(rs_out + 2);
+    ma[0] = maxabs[0];
+    ma[1] = maxabs[1];
+  }
+  for (int t = threadIdx.x; t < n_root_tasks; t += blockDim.x) {
+    const long long b = (long long)t * rpt;
+    root_tasks[t] =
+        BlockTask{0, (int)b, (int)std::min<long long>(b + rpt, n), 0};
+  }
 }
 
 __global__ void SubtractHistKernel(const int64_t* __restrict__ parents,
@@ -583,6 +611,54 @@ extern "C" {
 void* gbt_driver_create() { return new DriverCtx(); }
 void gbt_driver_destroy(void* ctx) { delete (DriverCtx*)ctx; }
 
+// Test hook: run the whole-tree chain's init kernel for an n_rows root
+// and compare the root hist task list it writes with ChunkTasks over the
+// same root node.  Returns the number of differing tasks (0 = equal, a
+// length mismatch counts), negative on a HIP error.
+int gbt_root_tasks_check(long long n_rows, long long min_rows,
+                         long long target_tasks, void* stream_v) {
+  hipStream_t stream = (hipStream_t)stream_v;
+  Node root{};
+  root.seg_end = (int)n_rows;
+  std::vector<Node*> nodes{&root};
+  std::vector<BlockTask> want;
+  ChunkTasks(nodes, &want, min_rows, target_tasks);
+  const long long rpt = RootRowsPerTask(n_rows, min_rows, target_tasks);
+  const int nt = RootTaskCount(n_rows, rpt);
+  // layout: [0,64) scalars | [64,128) sums+maxabs in | [128,192) out |
+  // tasks | row ids
+  const size_t o_tasks = 192;
+  const size_t o_ridx = o_tasks + (size_t)nt * sizeof(BlockTask);
+  const size_t bytes = o_ridx + (size_t)std::max<long long>(n_rows, 1) * 4;
+  char* d = nullptr;
+  HIP_CHECK(hipMalloc((void**)&d, bytes));
+  int rc = 0;
+  std::vector<BlockTask> got(nt);
+  hipError_t e = hipMemsetAsync(d, 0, o_tasks, stream);
+  if (e == hipSuccess) {
+    int32_t* sc = (int32_t*)d;
+    hipLaunchKernelGGL(WtInitKernel, dim3(2), dim3(256), 0, stream,
+                       (int32_t*)(d + o_ridx), n_rows, (int64_t*)nullptr,
+                       0LL, sc, sc + 1, sc + 2, (BlockTask*)(d + o_tasks),
+                       nt, rpt, (const int64_t*)(d + 64),
+                       (const float*)(d + 80), (int64_t*)(d + 128));
+    e = hipMemcpyAsync(got.data(), d + o_tasks,
+                       (size_t)nt * sizeof(BlockTask), hipMemcpyDeviceToHost,
+                       stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  (void)hipFree(d);
+  if (e != hipSuccess) return -(int)e;
+  if (want.size() != got.size()) return (int)std::max(want.size(), got.size());
+  for (size_t i = 0; i < want.size(); ++i) {
+    if (want[i].out_slot != got[i].out_slot ||
+        want[i].row_begin != got[i].row_begin ||
+        want[i].row_end != got[i].row_end)
+      ++rc;
+  }
+  return rc;
+}
+
 typedef void (*AllreduceFn)(long long* dev_ptr, long long n_elems);
 
 // Returns n_nodes (>0) on success, negative on failure.
@@ -678,6 +754,18 @@ int gbt_grow_tree(
     return v >= 64 && v <= 16384 ? v : 256;
   }();
   const long long hist_min_rows = 2048;
+  // partition task granularity (whole-tree chain): every block makes one
+  // returning atomic pair on its node's counter line, so at the top
+  // levels the block count, not the traffic, sets the kernel time.
+  // Swept 1024 / 2048 / 4096 / 8192: 975 / 1018 / 1023 / 892 rounds/s
+  // (profiles/r03_bench_kernels_chain.md); 4096 is the largest task of
+  // the partition kernel's register path.  Env GBT_PART_ROWS to tune; a
+  // power of two.
+  static long long part_min_rows = [] {
+    const char* e = getenv("GBT_PART_ROWS");
+    long long v = e ? atoll(e) : 4096;
+    return v >= 1024 && v <= 65536 && (v & (v - 1)) == 0 ? v : 4096;
+  }();
 
   // ---- root histogram: tasks host-generated (root segment is known)
   if (!whole_tree) {
@@ -827,10 +915,15 @@ int gbt_grow_tree(
       off = (off + bytes + 255) & ~255ULL;
       return o;
     };
+    // readback span: everything the host replay needs sits contiguously
+    // at the head of the arena, so ONE D2H copy returns it
     const size_t o_best = carve((size_t)rec_slots * 6 * 8);
     const size_t o_seg = carve((size_t)rec_slots * 2 * 4);
-    const size_t o_kn = carve((size_t)(max_depth + 2) * 4);
     const size_t o_kp = carve((size_t)(max_depth + 2) * 4);
+    const size_t o_mode = carve((size_t)max_depth * pool);
+    const size_t o_rs = carve(24);  // root sums [2] i64 + max-abs [2] f32
+    const size_t r_total = o_rs + 24;
+    const size_t o_kn = carve((size_t)(max_depth + 2) * 4);
     const size_t o_descw = carve((size_t)pool * 16);
     const size_t o_featw = carve((size_t)pool * 4);
     const size_t o_sbinw = carve((size_t)pool * 4);
@@ -843,7 +936,6 @@ int gbt_grow_tree(
     const size_t o_psb = carve((size_t)pool * 16);
     const size_t o_bnda = has_mono ? carve((size_t)pool * 16) : 0;
     const size_t o_bndb = has_mono ? carve((size_t)pool * 16) : 0;
-    const size_t o_mode = carve((size_t)max_depth * pool);
     if ((long long)off > wt_ws_bytes) return -9997;
     char* w = (char*)wt_ws;
     int64_t* best_rec = (int64_t*)(w + o_best);
@@ -864,64 +956,32 @@ int gbt_grow_tree(
         has_mono ? (double*)(w + o_bndb) : nullptr};
     uint8_t* d_mode = (uint8_t*)(w + o_mode);  // [max_depth][pool]
 
-    // root tasks: regenerated each call with IDENTICAL content (they
-    // depend only on n_rows and the task constants) and staged through
-    // the DEDICATED pinned const buffer, so a captured graph can bake
-    // the addresses and every replay re-reads the rewritten bytes.
-    // Layout: [0..15] kn/kp/seg init ints, then the root BlockTasks.
-    std::vector<BlockTask> rtasks;
-    {
-      std::vector<Node*> rnodes{&root};
-      ChunkTasks(rnodes, &rtasks, hist_min_rows, hist_tasks);
-    }
-    const size_t c_tasks_off = 16;
-    if (int e = ctx->ensure_const(c_tasks_off +
-                                  rtasks.size() * sizeof(BlockTask)))
-      return e;
-    {
-      int32_t* hh = (int32_t*)ctx->wtc_host;
-      hh[0] = 1;
-      hh[1] = 0;
-      hh[2] = 0;
-      hh[3] = (int)n_rows;
-      memcpy((char*)ctx->wtc_host + c_tasks_off, rtasks.data(),
-             rtasks.size() * sizeof(BlockTask));
-    }
+    // root hist tasks: a function of the configuration only, written on
+    // device by the chain's init kernel into the hist task buffer (the
+    // level-0 task generation overwrites it after the root hist has run)
+    const long long root_rpt =
+        RootRowsPerTask(n_rows, hist_min_rows, hist_tasks);
+    const int n_root_tasks = RootTaskCount(n_rows, root_rpt);
+    if (n_root_tasks > hist_tasks_cap) return -9996;
+    int64_t* d_rs = (int64_t*)(w + o_rs);
     const int wt_max_htasks = (int)std::min<long long>(
         std::min<long long>(n_rows / hist_min_rows, hist_tasks) +
             max_nodes_level + 1,
         (long long)hist_tasks_cap);
-    // pre-size the ONE readback so its (graph-baked) address is final
-    size_t r_best = 0;
-    size_t r_seg = ((size_t)rec_slots * 48 + 63) & ~63ULL;
-    size_t r_kp = (r_seg + (size_t)rec_slots * 8 + 63) & ~63ULL;
-    size_t r_rs = (r_kp + (size_t)(max_depth + 2) * 4 + 63) & ~63ULL;
-    size_t r_ma = r_rs + 16;
-    size_t r_mode = (r_ma + 8 + 63) & ~63ULL;
-    size_t r_total = r_mode + (size_t)max_depth * pool;
+    // partition launch grid: sum over nodes of ceil(rows / rows-per-task)
+    const int n_ptasks = (int)std::min<long long>(
+        n_rows / part_min_rows + pool + 2, (long long)wt_max_ptasks);
+    // pre-size the ONE readback so its (graph-baked) address is final;
+    // host offsets equal the arena offsets of the readback span
     if (int e = ctx->ensure_readback(r_total)) return e;
     char* rb = (char*)ctx->readback_host;
 
     // ---- the chain: EVERY launch for the whole tree, no host sync.
     // Ping-pong pointers are locals so a graph REPLAY (which skips this
-    // code entirely) leaves the outer state identical.
-    // H2D staging: tiny constant uploads, enqueued directly each call
-    // (kept OUT of the captured graph — graph-embedded memcpy nodes
-    // showed unreliable replay ordering on ROCm)
-    auto stage_h2d = [&](hipStream_t cs) -> int {
-      char* ch = (char*)ctx->wtc_host;
-      HIP_CHECK(hipMemcpyAsync(kn_arr, ch, 4, hipMemcpyHostToDevice,
-                               cs));
-      HIP_CHECK(hipMemcpyAsync(kp_arr, ch + 4, 4, hipMemcpyHostToDevice,
-                               cs));
-      HIP_CHECK(hipMemcpyAsync(seg_rec, ch + 8, 8, hipMemcpyHostToDevice,
-                               cs));
-      HIP_CHECK(hipMemcpyAsync((char*)ctx->wtc_dev + c_tasks_off,
-                               ch + c_tasks_off,
-                               rtasks.size() * sizeof(BlockTask),
-                               hipMemcpyHostToDevice, cs));
-      return 0;
-    };
+    // code entirely) leaves the outer state identical.  No host<->device
+    // copy is part of it (graph-embedded memcpy/memset nodes showed
+    // unreliable replay ordering on ROCm): constants are written and
+    // buffers zeroed by kernels.
     auto enqueue_chain = [&](hipStream_t cs) -> int {
       int32_t* cr = ridx;
       int32_t* ar = ridx_out;
@@ -929,19 +989,15 @@ int gbt_grow_tree(
       int64_t* np2 = hist_pool_b;
       {
         int blocks = (int)std::min<long long>((n_rows + 255) / 256, 4096);
-        hipLaunchKernelGGL(IotaKernel, dim3(blocks), dim3(256), 0, cs,
-                           cr, n_rows);
-      }
-      {
-        // zero via a kernel, not hipMemsetAsync: memset NODES in a
-        // captured graph replay out of order on this ROCm
-        int zb = (int)std::min<long long>((hist_row + 255) / 256, 4096);
-        hipLaunchKernelGGL(ZeroI64Kernel, dim3(zb), dim3(256), 0, cs, cp,
-                           hist_row);
+        hipLaunchKernelGGL(WtInitKernel, dim3(std::max(blocks, 1)),
+                           dim3(256), 0, cs, cr, n_rows, cp, hist_row,
+                           kn_arr, kp_arr, seg_rec, hist_tasks_dev,
+                           n_root_tasks, root_rpt, root_sums_dev, maxabs_dev,
+                           d_rs);
       }
       gbt_hist(gidx8, gidx16, n_features, qgpair, cr,
-               (const BlockTask*)((char*)ctx->wtc_dev + c_tasks_off),
-               (int)rtasks.size(), cp, n_bins, feat_group_start_dev,
+               hist_tasks_dev, n_root_tasks, cp, n_bins,
+               feat_group_start_dev,
                bin_group_start_dev, n_groups, max_group_bins, cut_ptrs_dev,
                use_shared, nullptr, cs);
       if (allreduce) allreduce((long long*)cp, hist_row);
@@ -970,7 +1026,7 @@ int gbt_grow_tree(
         hipLaunchKernelGGL(ApplyKernel, dim3(1), dim3(256), 0, cs, bl,
                            sl, kn_arr + L, kp_arr + L, ps_prev, gamma,
                            cut_ptrs_dev,
-                           (long long)1024, (long long)2048, wt_max_ptasks,
+                           part_min_rows, (long long)2048, n_ptasks,
                            kn_arr + L + 1, kp_arr + L + 1, d_feat, d_sbin,
                            d_dl, d_cnt, d_pt, d_desc, d_pps, d_pslot,
                            choice_global, maxabs_dev,
@@ -982,7 +1038,7 @@ int gbt_grow_tree(
                            L == 0 ? nullptr : d_mode + (size_t)(L - 1) * pool);
         gbt_partition(gidx8, gidx16, n_features, gidx8_col, gidx16_col,
                       n_rows, cr, ar, d_pt,
-                      wt_max_ptasks, d_feat, d_sbin, d_dl, nullptr, nullptr,
+                      n_ptasks, d_feat, d_sbin, d_dl, nullptr, nullptr,
                       n_bins_feat_dev, d_cnt, cs);
         std::swap(cr, ar);
         hipLaunchKernelGGL(HistTaskGenKernel, dim3(1), dim3(256), 0, cs,
@@ -992,6 +1048,8 @@ int gbt_grow_tree(
                            allreduce != nullptr ? 2 * cap_kids : 0,
                            d_mode + (size_t)L * pool);
         {
+          // zero via a kernel, not hipMemsetAsync: memset NODES in a
+          // captured graph replay out of order on this ROCm
           const long long zn = (long long)cap_kids * hist_row;
           int zb = (int)std::min<long long>((zn + 255) / 256, 4096);
           hipLaunchKernelGGL(ZeroI64Kernel, dim3(zb), dim3(256), 0, cs,
@@ -1003,8 +1061,9 @@ int gbt_grow_tree(
                  cut_ptrs_dev, use_shared, ps_next, cs);
         if (allreduce) {
           // fixed worst-case counts (host-known, rank-identical): built
-          // hist slots 0..cap/2-1 (unused slots are zeros — the memset
-          // covers the pool, HistTaskGenKernel zeroed the ps padding)
+          // hist slots 0..cap/2-1 (unused slots are zeros — the zero
+          // kernel covers the pool, HistTaskGenKernel zeroed the ps
+          // padding)
           // and the built-child pair sums.  Sibling subtraction AFTER
           // the reduce yields global histograms/sums for every child.
           allreduce((long long*)np2,
@@ -1034,23 +1093,10 @@ int gbt_grow_tree(
       }
       return 0;
     };
-    // D2H readback burst: direct enqueue after the kernels (not a graph
-    // node), the ONE sync follows
+    // D2H readback: ONE copy of the arena's readback span, enqueued
+    // directly after the kernels (not a graph node); the ONE sync follows
     auto readback = [&](hipStream_t cs) -> int {
-      HIP_CHECK(hipMemcpyAsync(rb + r_best, best_rec,
-                               (size_t)rec_slots * 48,
-                               hipMemcpyDeviceToHost, cs));
-      HIP_CHECK(hipMemcpyAsync(rb + r_seg, seg_rec, (size_t)rec_slots * 8,
-                               hipMemcpyDeviceToHost, cs));
-      HIP_CHECK(hipMemcpyAsync(rb + r_kp, kp_arr,
-                               (size_t)(max_depth + 2) * 4,
-                               hipMemcpyDeviceToHost, cs));
-      HIP_CHECK(hipMemcpyAsync(rb + r_rs, root_sums_dev, 16,
-                               hipMemcpyDeviceToHost, cs));
-      HIP_CHECK(hipMemcpyAsync(rb + r_ma, maxabs_dev, 8,
-                               hipMemcpyDeviceToHost, cs));
-      HIP_CHECK(hipMemcpyAsync(rb + r_mode, d_mode,
-                               (size_t)max_depth * pool,
+      HIP_CHECK(hipMemcpyAsync(rb, w + o_best, r_total,
                                hipMemcpyDeviceToHost, cs));
       return 0;
     };
@@ -1086,8 +1132,6 @@ int gbt_grow_tree(
           (unsigned long long)maxabs_dev, (unsigned long long)monotone_dev,
           (unsigned long long)fmask_dev,
           (unsigned long long)ctx->readback_host,
-          (unsigned long long)ctx->wtc_host,
-          (unsigned long long)ctx->wtc_dev,
           (unsigned long long)n_rows, (unsigned long long)n_features,
           (unsigned long long)n_bins, (unsigned long long)use_shared,
           (unsigned long long)n_groups,
@@ -1096,7 +1140,11 @@ int gbt_grow_tree(
           (unsigned long long)max_nodes_level,
           (unsigned long long)wt_max_ptasks,
           (unsigned long long)hist_tasks_cap,
-          (unsigned long long)rtasks.size(),
+          (unsigned long long)n_root_tasks,
+          (unsigned long long)root_rpt,
+          (unsigned long long)part_min_rows,
+          (unsigned long long)n_ptasks,
+          (unsigned long long)wt_max_htasks,
           (unsigned long long)has_mono,
           db(reg_lambda), db(reg_alpha), db(max_delta_step),
           db(min_child_weight), db(gamma)};
@@ -1109,7 +1157,6 @@ int gbt_grow_tree(
       HIP_CHECK(hipEventRecord(ctx->gevent, stream));
       HIP_CHECK(hipEventSynchronize(ctx->gevent));
       if (ctx->wt_graph != nullptr && key == ctx->wt_key) {
-        if (int e = stage_h2d(ctx->gstream)) return e;
         if (hipGraphLaunch(ctx->wt_graph, ctx->gstream) == hipSuccess) {
           enqueued = true;
           if (WtGraphDebug()) fprintf(stderr, "[wtgraph] replay\n");
@@ -1124,7 +1171,6 @@ int gbt_grow_tree(
         // first sighting of this configuration: run direct, remember it
         ctx->wt_seen_key = key;
       } else if (!enqueued) {
-        if (int e = stage_h2d(ctx->gstream)) return e;
         if (hipStreamBeginCapture(ctx->gstream,
                                   hipStreamCaptureModeRelaxed) !=
             hipSuccess) {
@@ -1183,7 +1229,6 @@ int gbt_grow_tree(
     }
     if (!enqueued) {
       if (WtGraphDebug()) fprintf(stderr, "[wtgraph] direct enqueue\n");
-      if (int e = stage_h2d(stream)) return e;
       if (int e = enqueue_chain(stream)) return e;
       if (int e = readback(stream)) return e;
     } else {
@@ -1194,12 +1239,12 @@ int gbt_grow_tree(
     // the chain used local ping-pong pointers; reproduce the final
     // parity for the post-sync leaf decide ((max_depth-1) swaps)
     if ((max_depth - 1) & 1) std::swap(cur_ridx, alt_ridx);
-    const int64_t* h_best = (const int64_t*)(rb + r_best);
-    const int32_t* h_seg = (const int32_t*)(rb + r_seg);
-    const int32_t* h_kp = (const int32_t*)(rb + r_kp);
-    const int64_t* h_rs = (const int64_t*)(rb + r_rs);
-    const float* h_ma = (const float*)(rb + r_ma);
-    const uint8_t* h_mode = (const uint8_t*)(rb + r_mode);
+    const int64_t* h_best = (const int64_t*)(rb + o_best);
+    const int32_t* h_seg = (const int32_t*)(rb + o_seg);
+    const int32_t* h_kp = (const int32_t*)(rb + o_kp);
+    const int64_t* h_rs = (const int64_t*)(rb + o_rs);
+    const float* h_ma = (const float*)(rb + o_rs + 16);
+    const uint8_t* h_mode = (const uint8_t*)(rb + o_mode);
     g_scale = h_ma[0] > 0.f ? 1073741824.0 / (double)h_ma[0] : 1.0;
     h_scale = h_ma[1] > 0.f ? 1073741824.0 / (double)h_ma[1] : 1.0;
     inv_g = 1.0 / g_scale;

@@ -3,20 +3,33 @@
 //
 // Reference behavior: src/tree/gpu_hist/row_partitioner.cuh (cub
 // DispatchScan partition + SortPositionCopyKernel).  MI355X re-design:
-// three-phase block-aggregated scatter —
-//   A) each thread counts left-rows in its contiguous sub-range,
-//   B) block scan of per-thread counts (wave64 shfl scan + LDS wave
-//      totals), one atomicAdd/atomicSub PER BLOCK reserves the global
-//      left/right windows (profiling showed per-wave atomics on the
-//      per-node counters serialize: 273us/launch -> ~10us),
-//   C) threads re-read their sub-range and write destinations.
-// Stable within a block; histogram sums are order-independent anyway
-// (int64 fixed point).
+// wave-tiled, ballot-based block-aggregated scatter —
+//   A) each wave walks tiles of 64 CONSECUTIVE ridx_in entries (one
+//      coalesced load per tile), gathers the bin and takes the wave
+//      ballot of the go-left decision; left counts are popcounts,
+//   B) ONE atomicAdd/atomicSub PER BLOCK reserves the global left/right
+//      windows (profiling showed per-wave atomics on the per-node
+//      counters serialize: 273us/launch -> ~10us),
+//   C) a lane's destination is window base + mbcnt(ballot), so each
+//      side's stores are contiguous within the wave.
+// Row ids and ballots stay in registers between A and C for tasks of up
+// to kPartCacheRows rows; larger tasks re-load and re-gather in C.
+// Order within a side is unspecified; histogram sums are
+// order-independent anyway (int64 fixed point).
 #include "gbt_kernels.h"
 
 #ifndef GBT_PART_BLOCK
 #define GBT_PART_BLOCK 256
 #endif
+
+namespace {
+constexpr int kPartWaves = GBT_PART_BLOCK / 64;
+// register-cached tiles per wave: 4 covers the 1024-row tasks, 16 the
+// coarser task sizes (4096 rows per block)
+constexpr int kPartTilesSmall = 4;
+constexpr int kPartTilesLarge = 16;
+constexpr int kPartCacheRows = kPartTilesLarge * 64 * kPartWaves;
+}  // namespace
 
 __device__ __forceinline__ bool DecideLeft(int local_bin, int fbins,
                                            int split_bin_local,
@@ -33,6 +46,141 @@ __device__ __forceinline__ bool DecideLeft(int local_bin, int fbins,
     return !in_set;
   }
   return local_bin <= split_bin_local;
+}
+
+// per-block split description, shared by the count and scatter phases
+template <typename BinT>
+struct PartSplit {
+  const BinT* gidx;
+  const BinT* col;  // the split feature's column, or null (row-major)
+  int n_features, feature, fbins, sbin, cat_words;
+  bool dleft;
+  const uint32_t* cats;
+
+  __device__ __forceinline__ bool Left(int row) const {
+    const int local = col ? (int)col[row]
+                          : (int)gidx[(size_t)row * n_features + feature];
+    return DecideLeft(local, fbins, sbin, dleft, cats, cat_words);
+  }
+};
+
+// number of set bits of a wave mask below this lane
+__device__ __forceinline__ int LanesBelow(unsigned long long m) {
+  return (int)__builtin_amdgcn_mbcnt_hi(
+      (unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+// phase B: one reservation per block on the node's counter pair;
+// returns this wave's first left / right destination
+__device__ __forceinline__ void ReserveWindows(int wave_left, int wave_right,
+                                               int32_t* counters, int slot,
+                                               int* dl, int* dr) {
+  __shared__ int s_left[kPartWaves], s_right[kPartWaves];
+  __shared__ int s_base_l, s_base_r;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    s_left[wave] = wave_left;
+    s_right[wave] = wave_right;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot_l = 0, tot_r = 0;
+    for (int w = 0; w < kPartWaves; ++w) {
+      tot_l += s_left[w];
+      tot_r += s_right[w];
+    }
+    s_base_l = tot_l ? atomicAdd(&counters[2 * slot], tot_l) : 0;
+    s_base_r = tot_r ? atomicSub(&counters[2 * slot + 1], tot_r) - tot_r : 0;
+  }
+  __syncthreads();
+  int l = s_base_l, r = s_base_r;
+  for (int w = 0; w < wave; ++w) {
+    l += s_left[w];
+    r += s_right[w];
+  }
+  *dl = l;
+  *dr = r;
+}
+
+// Tasks of up to TILES * 64 * kPartWaves rows: tile j of wave w covers
+// entries [begin + (j * kPartWaves + w) * 64, +64).  Straight-line code
+// (no per-tile branch) so the TILES loads and gathers issue back to back.
+template <typename BinT, int TILES>
+__device__ __forceinline__ void PartitionCached(
+    const PartSplit<BinT>& sp, const int32_t* __restrict__ ridx_in,
+    int32_t* __restrict__ ridx_out, int begin, int end, int slot,
+    int32_t* counters) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  int rows[TILES];
+  unsigned long long lmask[TILES];
+  int wave_left = 0, wave_rows = 0;
+#pragma unroll
+  for (int j = 0; j < TILES; ++j) {
+    const int i = begin + (j * kPartWaves + wave) * 64 + lane;
+    const bool valid = i < end;
+    // clamped: lanes past the task re-read its last entry (in bounds)
+    rows[j] = ridx_in[min(i, end - 1)];
+    lmask[j] = __ballot(sp.Left(rows[j]) && valid);
+    wave_left += __popcll(lmask[j]);
+    wave_rows += __popcll(__ballot(valid));
+  }
+  int dl, dr;
+  ReserveWindows(wave_left, wave_rows - wave_left, counters, slot, &dl, &dr);
+#pragma unroll
+  for (int j = 0; j < TILES; ++j) {
+    const int i = begin + (j * kPartWaves + wave) * 64 + lane;
+    const bool valid = i < end;
+    const unsigned long long lm = lmask[j];
+    const unsigned long long rm = __ballot(valid) & ~lm;
+    if (valid) {
+      if ((lm >> lane) & 1ull) {
+        ridx_out[dl + LanesBelow(lm)] = rows[j];
+      } else {
+        ridx_out[dr + LanesBelow(rm)] = rows[j];
+      }
+    }
+    dl += __popcll(lm);
+    dr += __popcll(rm);
+  }
+}
+
+// Tasks beyond the register budget: count, then re-load and re-gather.
+template <typename BinT>
+__device__ __forceinline__ void PartitionRegather(
+    const PartSplit<BinT>& sp, const int32_t* __restrict__ ridx_in,
+    int32_t* __restrict__ ridx_out, int begin, int end, int slot,
+    int32_t* counters) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  int wave_left = 0, wave_rows = 0;
+  for (int t0 = begin + wave * 64; t0 < end; t0 += kPartWaves * 64) {
+    const int i = t0 + lane;
+    const bool valid = i < end;
+    const int row = ridx_in[min(i, end - 1)];
+    wave_left += __popcll(__ballot(sp.Left(row) && valid));
+    wave_rows += __popcll(__ballot(valid));
+  }
+  int dl, dr;
+  ReserveWindows(wave_left, wave_rows - wave_left, counters, slot, &dl, &dr);
+  for (int t0 = begin + wave * 64; t0 < end; t0 += kPartWaves * 64) {
+    const int i = t0 + lane;
+    const bool valid = i < end;
+    const int row = ridx_in[min(i, end - 1)];
+    const bool left = sp.Left(row) && valid;
+    const unsigned long long lm = __ballot(left);
+    const unsigned long long rm = __ballot(valid) & ~lm;
+    if (valid) {
+      if (left) {
+        ridx_out[dl + LanesBelow(lm)] = row;
+      } else {
+        ridx_out[dr + LanesBelow(rm)] = row;
+      }
+    }
+    dl += __popcll(lm);
+    dr += __popcll(rm);
+  }
 }
 
 // gidx_col: optional FEATURE-MAJOR copy of the bin matrix ([F][ld]).
@@ -56,110 +204,35 @@ __global__ __launch_bounds__(GBT_PART_BLOCK) void PartitionKernel(
   const BlockTask task = tasks[blockIdx.x];
   if (task.row_begin >= task.row_end) return;  // padded empty task
   const int slot = task.out_slot;
-  const int feature = split_feature[slot];
-  const int sbin = split_bin_local[slot];
-  const bool dleft = default_left[slot] != 0;
-  const int fbins = n_bins_feat[feature];
-  const uint32_t* cats = nullptr;
-  int cat_words = 0;
+  PartSplit<BinT> sp;
+  sp.gidx = gidx;
+  sp.n_features = n_features;
+  sp.feature = split_feature[slot];
+  sp.sbin = split_bin_local[slot];
+  sp.dleft = default_left[slot] != 0;
+  sp.fbins = n_bins_feat[sp.feature];
+  sp.cats = nullptr;
+  sp.cat_words = 0;
   if (cat_bits_offset != nullptr) {
     const int c0 = cat_bits_offset[slot];
-    cat_words = cat_bits_offset[slot + 1] - c0;
-    if (cat_words > 0) cats = cat_bits + c0;
+    sp.cat_words = cat_bits_offset[slot + 1] - c0;
+    if (sp.cat_words > 0) sp.cats = cat_bits + c0;
   }
+  sp.col = gidx_col ? gidx_col + (size_t)sp.feature * col_ld : nullptr;
 
+  // block-uniform dispatch on the task size
   const int n_rows = task.row_end - task.row_begin;
-  const int chunk = (n_rows + (int)blockDim.x - 1) / (int)blockDim.x;
-  const int my_begin = task.row_begin + (int)threadIdx.x * chunk;
-  const int my_end = min(my_begin + chunk, task.row_end);
-
-  // decision cache: avoid the second gather pass when the task fits
-  // the LDS bitmask (64K rows = 8 KiB)
-  constexpr int kMaxCacheRows = 65536;
-  __shared__ uint32_t decide_bits[kMaxCacheRows / 32];
-  const bool use_cache = n_rows <= kMaxCacheRows;
-  if (use_cache) {
-    const int n_words = (n_rows + 31) / 32;
-    for (int i = threadIdx.x; i < n_words; i += blockDim.x) {
-      decide_bits[i] = 0u;
-    }
-    __syncthreads();
-  }
-
-  const BinT* col = gidx_col ? gidx_col + (size_t)feature * col_ld
-                             : nullptr;
-  // phase A: count left in my contiguous sub-range
-  int my_left = 0;
-  for (int i = my_begin; i < my_end; ++i) {
-    const int row = ridx_in[i];
-    const int local = col ? (int)col[row]
-                          : (int)gidx[(size_t)row * n_features + feature];
-    const bool left = DecideLeft(local, fbins, sbin, dleft, cats, cat_words);
-    my_left += left ? 1 : 0;
-    if (use_cache) {
-      const int k = i - task.row_begin;
-      // each thread owns a contiguous bit range; no races within a word
-      // except at range boundaries -> use atomicOr for safety
-      if (left) atomicOr(&decide_bits[k >> 5], 1u << (k & 31));
-    }
-  }
-  const int my_rows = max(my_end - my_begin, 0);
-  const int my_right = my_rows - my_left;
-
-  // phase B: block exclusive scan of (left, right) counts
-  __shared__ int wave_left[GBT_PART_BLOCK / 64];
-  __shared__ int wave_right[GBT_PART_BLOCK / 64];
-  __shared__ int base_l, base_r;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  int scan_l = my_left, scan_r = my_right;
-  for (int off = 1; off < 64; off <<= 1) {
-    const int tl = __shfl_up(scan_l, off, 64);
-    const int tr = __shfl_up(scan_r, off, 64);
-    if (lane >= off) {
-      scan_l += tl;
-      scan_r += tr;
-    }
-  }
-  if (lane == 63) {
-    wave_left[wave] = scan_l;
-    wave_right[wave] = scan_r;
-  }
-  __syncthreads();
-  int wl_off = 0, wr_off = 0;
-  for (int w = 0; w < wave; ++w) {
-    wl_off += wave_left[w];
-    wr_off += wave_right[w];
-  }
-  const int excl_l = scan_l - my_left + wl_off;  // exclusive prefix
-  const int excl_r = scan_r - my_right + wr_off;
-  if (threadIdx.x == (int)blockDim.x - 1) {
-    const int tot_l = excl_l + my_left;
-    const int tot_r = excl_r + my_right;
-    base_l = tot_l ? atomicAdd(&counters[2 * slot], tot_l) : 0;
-    base_r = tot_r ? atomicSub(&counters[2 * slot + 1], tot_r) - tot_r : 0;
-  }
-  __syncthreads();
-
-  // phase C: scatter (cached decisions when they fit, else re-gather)
-  int dl = base_l + excl_l;
-  int dr = base_r + excl_r;
-  for (int i = my_begin; i < my_end; ++i) {
-    const int row = ridx_in[i];
-    bool left;
-    if (use_cache) {
-      const int k = i - task.row_begin;
-      left = (decide_bits[k >> 5] >> (k & 31)) & 1u;
-    } else {
-      const int local = col ? (int)col[row]
-                            : (int)gidx[(size_t)row * n_features + feature];
-      left = DecideLeft(local, fbins, sbin, dleft, cats, cat_words);
-    }
-    if (left) {
-      ridx_out[dl++] = row;
-    } else {
-      ridx_out[dr++] = row;
-    }
+  if (n_rows <= kPartTilesSmall * 64 * kPartWaves) {
+    PartitionCached<BinT, kPartTilesSmall>(sp, ridx_in, ridx_out,
+                                           task.row_begin, task.row_end, slot,
+                                           counters);
+  } else if (n_rows <= kPartCacheRows) {
+    PartitionCached<BinT, kPartTilesLarge>(sp, ridx_in, ridx_out,
+                                           task.row_begin, task.row_end, slot,
+                                           counters);
+  } else {
+    PartitionRegather<BinT>(sp, ridx_in, ridx_out, task.row_begin,
+                            task.row_end, slot, counters);
   }
 }
 
