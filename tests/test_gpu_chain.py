@@ -173,7 +173,7 @@ def test_root_tasks_match_chunk_tasks(n_rows, min_rows, target):
 # whole chain vs the python GPU driver
 
 _TREE_FIELDS = ("left", "right", "split_index", "split_cond", "default_left",
-                "loss_chg")
+                "loss_chg", "sum_hess", "base_weight")
 
 
 def _chain_data(n, f=10, seed=11):
@@ -201,10 +201,16 @@ def _gpair_step(n, seed):
     return torch.tensor(np.stack([g, h], axis=1))
 
 
-def check_chain(n, params, seeds=(3, 4, 5), make_gpair=_gpair):
+def check_chain(n, params, seeds=(3, 4, 5), make_gpair=_gpair, monotone=None,
+                per_level=False):
     """Grow one tree per seed with the native chain on ONE GpuOps (call 1
     enqueues directly, call 2 captures the graph, call 3 replays it) and
-    compare each with the python driver's tree on a fresh GpuOps."""
+    compare each with the python driver's tree on a fresh GpuOps.
+
+    monotone: int8 constraint per feature for both drivers, or None.
+    per_level: hand the native side a quantizer without its device
+    max-abs, so gbt_grow_tree takes its per-level mode at any depth (the
+    host scales remain)."""
     from xgboost_amd.backend.gpu import GpuOps
     from xgboost_amd.grower import TreeGrower
     from xgboost_amd.tree_model import RegTree
@@ -216,17 +222,19 @@ def check_chain(n, params, seeds=(3, 4, 5), make_gpair=_gpair):
     for call, seed in enumerate(seeds):
         gpair = make_gpair(n, seed).cuda()
         quant = GradQuantizer(gpair)
+        if per_level:
+            del quant.maxabs_dev
         qg = quant.quantize(gpair)
         rs = qg.to(torch.int64).sum(dim=0).contiguous()
         res = gops.grow_tree_native(qg, RegTree(X.shape[1]), param, quant,
-                                    None, rs)
+                                    monotone, rs)
         assert res is not None, "native driver refused a supported config"
         t_native, pos_native = res
         pos_native = pos_native.clone()
 
         gops_py = GpuOps(qm.to("cuda"))
         quant_py = GradQuantizer(gpair)
-        grower = TreeGrower(gops_py, param, quant_py, n)
+        grower = TreeGrower(gops_py, param, quant_py, n, monotone=monotone)
         t_py, pos_py = grower._grow(quant_py.quantize(gpair),
                                     RegTree(X.shape[1]))
         torch.cuda.synchronize()
@@ -256,6 +264,53 @@ def test_chain_nodes_stop_early():
     n_split = check_chain(10007, {"max_depth": 6,
                                   "min_child_weight": 400.0})
     assert all(3 <= s < 31 for s in n_split), n_split
+
+
+_MONOTONE = np.array([1, -1] * 5, np.int8)  # every feature constrained
+
+
+def test_per_level_depth2():
+    # root eval sync, one partition level, the final-level leaf decide
+    assert min(check_chain(10007, {"max_depth": 2}, per_level=True)) >= 3
+
+
+def test_per_level_depth6():
+    # device sibling choice, pair sums on device
+    assert min(check_chain(10007, {"max_depth": 6, "reg_lambda": 1.2,
+                                   "min_child_weight": 2.0},
+                           per_level=True)) >= 3
+
+
+def test_per_level_nodes_stop_early():
+    # leaves at both ping-pong parities: the two-parity leaf sweep
+    n_split = check_chain(10007, {"max_depth": 6,
+                                  "min_child_weight": 400.0},
+                          per_level=True)
+    assert all(3 <= s < 31 for s in n_split), n_split
+
+
+def test_per_level_monotone():
+    # host sibling choice by hessian, staged sums and bounds
+    assert min(check_chain(10007, {"max_depth": 6}, monotone=_MONOTONE,
+                           per_level=True)) >= 3
+
+
+def test_chain_monotone_exact():
+    # ApplyKernel's bound propagation against the python driver's
+    assert min(check_chain(10007, {"max_depth": 6},
+                           monotone=_MONOTONE)) >= 3
+
+
+def test_chain_depth1():
+    # below the whole-tree gate: the root goes straight to leaf decide
+    assert check_chain(10007, {"max_depth": 1}) == [1, 1, 1]
+
+
+def test_chain_depth13_no_arena():
+    # too deep for the whole-tree arena: per-level mode without one
+    n_split = check_chain(10007, {"max_depth": 13,
+                                  "min_child_weight": 400.0})
+    assert all(s >= 3 for s in n_split), n_split
 
 
 def test_chain_children_do_not_split():

@@ -596,15 +596,9 @@ class GpuOps(SegmentedOpsMixin):
                 "eval_best": torch.empty((pool_rows, 6), dtype=torch.int64,
                                          device=dev),
                 "pos": torch.zeros(n_rows, dtype=torch.int32, device=dev),
-                # 1-sync driver: persistent partition counters (expand
-                # nodes per level <= 2^(max_depth-1)), device-generated
-                # hist task buffer + task-gen scratch
-                "counters": torch.empty(max(4, 1 << param.max_depth),
-                                        dtype=torch.int32, device=dev),
+                # device-generated hist task buffer
                 "hist_tasks_cap": 16384 + max_build + 8,
                 "hist_tasks": torch.empty((16384 + max_build + 8, 4),
-                                          dtype=torch.int32, device=dev),
-                "tg_scratch": torch.empty(3 * max_build + 8,
                                           dtype=torch.int32, device=dev),
                 # pointer-stable staging for the per-round inputs: the
                 # driver's hipGraph replay bakes device addresses, so
@@ -621,17 +615,13 @@ class GpuOps(SegmentedOpsMixin):
                 "driver": self.lib.gbt_driver_create(),
             }
             # whole-tree mode arena (single sync per tree): per-level
-            # best/segment records + device-side partition/task args
+            # best/segment records + device-side partition/task args;
+            # the driver owns its layout and reports its size
             pool = 2 * max_build
             if pool <= 2048:
-                rec = 1 + param.max_depth * pool
                 mp = n_rows // 1024 + pool + 2
-                # + 2 fp64 bound ping-pong buffers (monotone whole-tree)
-                # + per-level built-is-left mode records
-                # + the 24-byte root sums / max-abs readback slot
-                wt_bytes = (48 * rec + 8 * rec + 8 * (param.max_depth + 2)
-                            + 96 * pool + 32 * pool + 16 * mp
-                            + param.max_depth * pool + 24 + 32 * 1024)
+                wt_bytes = self.lib.gbt_wt_arena_bytes(param.max_depth,
+                                                       max_build, mp)
                 ws["wt_max_ptasks"] = mp
                 ws["wt_ws"] = torch.empty(wt_bytes, dtype=torch.uint8,
                                           device=dev)
@@ -716,8 +706,7 @@ class GpuOps(SegmentedOpsMixin):
             self.hip.ptr(ws["eval_dir"]), self.hip.ptr(ws["eval_lsum"]),
             self.hip.ptr(ws["eval_best"]), self.hip.ptr(ws["pos"]),
             max_build,
-            self.hip.ptr(ws["counters"]), self.hip.ptr(ws["hist_tasks"]),
-            ws["hist_tasks_cap"], self.hip.ptr(ws["tg_scratch"]),
+            self.hip.ptr(ws["hist_tasks"]), ws["hist_tasks_cap"],
             self.hip.ptr(ws["wt_ws"]),
             0 if ws["wt_ws"] is None else ws["wt_ws"].numel(),
             ws["wt_max_ptasks"],
@@ -733,7 +722,10 @@ class GpuOps(SegmentedOpsMixin):
                 "default_left", "loss_chg", "sum_hess", "base_weight")],
             self.hip.stream())
         if rc in (-9998, -9999):
-            return None  # capacity guard tripped: python driver handles it
+            # driver.hip's kCapacityTaskGenLds / kCapacityHistPool: a
+            # level wider than the native driver serves, not an error
+            # (the python driver handles it)
+            return None
         if rc <= 0:
             raise RuntimeError(f"gbt_grow_tree failed: rc={rc}")
         if ma is not None:

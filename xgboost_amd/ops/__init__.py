@@ -59,6 +59,7 @@ _SIGS = {
     "gbt_driver_create": [],
     "gbt_driver_destroy": [_p],
     "gbt_root_tasks_check": [_i64, _i64, _i64, _p],
+    "gbt_wt_arena_bytes": [_i, _i, _i],
     "gbt_grow_tree": [
         _p,                      # ctx
         _p, _p, _i,              # gidx8/16, n_features
@@ -69,7 +70,7 @@ _SIGS = {
         _p, _p, _p, _p,          # ridx, ridx_out, pool_a, pool_b
         _p, _p, _p, _p, _p, _p,  # eval_gain/bin/dir/lsum/best, pos_out
         _i,                      # max_nodes_level
-        _p, _p, _i, _p,          # part_counters, hist_tasks_dev, cap, tg_scratch
+        _p, _i,                  # hist_tasks_dev, cap
         _p, _i64, _i,            # wt_ws, wt_ws_bytes, wt_max_ptasks
         _p,                      # root_sums_dev [2] int64
         _p, _p,                  # maxabs_dev [2] f32 | out_scales [2] f64
@@ -121,6 +122,8 @@ def load() -> ctypes.CDLL:
         _lib.gbt_grow_tree.restype = _c.c_int
     if hasattr(_lib, "gbt_root_tasks_check"):
         _lib.gbt_root_tasks_check.restype = _c.c_int
+    if hasattr(_lib, "gbt_wt_arena_bytes"):
+        _lib.gbt_wt_arena_bytes.restype = _c.c_longlong
     if hasattr(_lib, "gbt_partition_cpu"):
         _lib.gbt_partition_cpu.restype = _c.c_longlong
     return _lib
