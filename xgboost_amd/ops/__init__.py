@@ -33,6 +33,13 @@ _SIGS = {
                       _p, _p, _p, _p, _p],
     "gbt_evaluate": [_p, _i, _i, _i, _p, _p, _p, _d, _d, _d, _d, _d, _d,
                      _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
+    # gbt_evaluate plus mask_stride; _ref is the single-wave reference
+    "gbt_evaluate_masked": [_p, _i, _i, _i, _p, _p, _p, _d, _d, _d, _d, _d,
+                            _d, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i,
+                            _p],
+    "gbt_evaluate_ref": [_p, _i, _i, _i, _p, _p, _p, _d, _d, _d, _d, _d,
+                         _d, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i,
+                         _p],
     "gbt_compress": [_p, _i64, _i, _p, _p, _p, _f, _i, _p, _p, _p],
     "gbt_predict": [_p, _i64, _i, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p,
                     _p, _p, _i, _i, _p, _p, _p],
