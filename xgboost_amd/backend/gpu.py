@@ -1267,3 +1267,74 @@ def predict_margin_q_gpu(booster, dmat, out: Optional[torch.Tensor],
                           None if out is None else out[s:e],
                           None if out_leaf is None else out_leaf[s:e])
     return out
+
+
+# ---------------------------------------------------------------------------
+# sparse CSR predictor (predict_csr.hip)
+
+def _upload_csr(csr, device):
+    """indptr int64 / indices int32 / values float32 of `csr` on `device`."""
+    return (torch.from_numpy(csr.indptr.astype(np.int64)).to(device),
+            torch.from_numpy(csr.indices.astype(np.int32)).to(device),
+            torch.from_numpy(csr.data.astype(np.float32)).to(device))
+
+
+def _device_csr(dmat, device):
+    """Device copy of a sparse DMatrix's CSR arrays, uploaded once per
+    device and kept on the DMatrix (an eval set is predicted every
+    round).  The kernel searches sorted rows: unsorted indices are sorted
+    in a copy, the matrix itself stays as the caller built it."""
+    cache = dmat.__dict__.setdefault("_device_csr_cache", {})
+    key = str(device)
+    ent = cache.get(key)
+    if ent is None:
+        csr = dmat.sparse_data()
+        if not csr.has_sorted_indices:
+            csr = csr.sorted_indices()
+        ent = cache[key] = _upload_csr(csr, device)
+    return ent
+
+
+def _launch_predict_csr(fa: _ForestQ, indptr: torch.Tensor,
+                        indices: torch.Tensor, values: torch.Tensor,
+                        n_features: int, out: Optional[torch.Tensor],
+                        out_leaf: Optional[torch.Tensor],
+                        force_search: int = 0, grid_cap: int = 0) -> None:
+    from .. import ops as hip_ops
+    lib = hip_ops.load()
+    n = indptr.shape[0] - 1
+    assert (indptr.dtype == torch.int64 and indices.dtype == torch.int32
+            and values.dtype == torch.float32)
+    assert out is None or (out.is_contiguous() and out.shape[0] == n
+                           and out.shape[1] == fa.n_outputs)
+    assert out_leaf is None or (out_leaf.is_contiguous()
+                                and out_leaf.dtype == torch.int32
+                                and out_leaf.shape == (n, fa.n_trees))
+    lib.gbt_predict_csr(
+        hip_ops.ptr(indptr), hip_ops.ptr(indices), hip_ops.ptr(values),
+        n, int(n_features), hip_ops.ptr(fa.nodes),
+        hip_ops.ptr(fa.tree_offsets), hip_ops.ptr(fa.cat_offsets),
+        hip_ops.ptr(fa.cat_bits), hip_ops.ptr(fa.tree_group),
+        hip_ops.ptr(fa.vec_offset), hip_ops.ptr(fa.leaf_vec), fa.n_trees,
+        fa.n_outputs, hip_ops.ptr(out), hip_ops.ptr(out_leaf),
+        int(force_search), int(grid_cap), hip_ops.stream())
+
+
+def predict_margin_csr_gpu(booster, dmat, out: Optional[torch.Tensor],
+                           lo: int, hi: int, idxs=None,
+                           out_leaf: Optional[torch.Tensor] = None,
+                           force_search: bool = False, grid_cap: int = 0):
+    """predict_margin_q_gpu for a sparse CSR DMatrix: add trees [lo, hi)
+    (or the DART subset `idxs`, never cached) to `out` and/or write leaf
+    ids to `out_leaf`.  Absent entries and stored NaNs are missing."""
+    device = out.device if out is not None else out_leaf.device
+    if idxs is not None:
+        fa = _ForestQ(booster, idxs, device, None)
+    else:
+        fa = _cached_forest_q(booster, lo, hi, device, None)
+    if fa.n_trees == 0 or dmat.num_row() == 0:
+        return out
+    indptr, indices, values = _device_csr(dmat, device)
+    _launch_predict_csr(fa, indptr, indices, values, dmat.num_col(), out,
+                        out_leaf, 1 if force_search else 0, grid_cap)
+    return out

@@ -349,6 +349,10 @@ class Booster:
         out = torch.zeros((n, self.n_outputs), dtype=torch.float32,
                           device=self.device)
         if getattr(dmat, "_sparse_data", None) is not None:
+            if self.device.type == "cuda" and len(idxs) > 0:
+                from .backend.gpu import predict_margin_csr_gpu
+                return predict_margin_csr_gpu(self, dmat, out, 0, 0,
+                                              idxs=list(idxs))
             return self._sparse_margin_add(dmat, out, list(idxs))
         from .extmem import ExtMemQuantileDMatrix
         if isinstance(dmat, ExtMemQuantileDMatrix):
@@ -954,7 +958,9 @@ class Booster:
         if isinstance(dmat, ExtMemQuantileDMatrix):
             return self._predict_margin_extmem(dmat, out, lo, hi)
         if getattr(dmat, "_sparse_data", None) is not None:
-            # sparse CSR stays on the host (no CSR predict kernel)
+            if self.device.type == "cuda" and hi > lo:
+                from .backend.gpu import predict_margin_csr_gpu
+                return predict_margin_csr_gpu(self, dmat, out, lo, hi)
             return self._predict_margin_sparse(dmat, out, lo, hi)
         train_cats = getattr(self, "cat_categories_", None)
         pred_cats = getattr(dmat, "categories_", None)
@@ -995,25 +1001,25 @@ class Booster:
                                lo: int, hi: int) -> torch.Tensor:
         return self._sparse_margin_add(dmat, out, list(range(lo, hi)))
 
-    def _sparse_margin_add(self, dmat, out: torch.Tensor,
-                           idxs: List[int]) -> torch.Tensor:
-        """Sparse predict: densify ONLY the features used by the trees,
-        absent entries become NaN (missing -> default direction)."""
-        if not idxs:
-            return out  # no trees yet (first margin of training)
+    def _sparse_leaf_ids(self, dmat, idxs: List[int]):
+        """Host sparse traversal: yields (t, leaf id per row) for the
+        trees `idxs`.  Densifies ONLY the features used by the trees,
+        absent entries become NaN (missing -> default direction); a
+        split on a column the matrix does not have is missing too."""
         csr = dmat.sparse_data()
-        n = csr.shape[0]
+        n, n_col = csr.shape
         used = sorted(set(
             int(f) for t in idxs
             for nid in range(self.trees[t].n_nodes)
             if not self.trees[t].is_leaf(nid)
             for f in [self.trees[t].split_index[nid]]))
-        if not used:
-            return out
         col_of = {f: i for i, f in enumerate(used)}
-        sub = csr[:, used].tocoo()
         X_sub = np.full((n, len(used)), np.nan, dtype=np.float32)
-        X_sub[sub.row, sub.col] = sub.data
+        present = [f for f in used if f < n_col]
+        if present:
+            sub = csr[:, present].tocoo()
+            dst = np.asarray([col_of[f] for f in present], np.int64)
+            X_sub[sub.row, dst[sub.col]] = sub.data
         for t in idxs:
             tree = self.trees[t]
             remap = tree.split_index[:tree.n_nodes].copy()
@@ -1026,9 +1032,21 @@ class Booster:
                 pos = tree.predict_leaf_np(X_sub, np.nan)
             finally:
                 tree.split_index[:tree.n_nodes] = saved
-            vals = tree.split_cond[:tree.n_nodes][pos]
-            out[:, self.tree_info[t]] += self._tw(t) * torch.as_tensor(
-                vals, device=out.device)
+            yield t, pos
+
+    def _sparse_margin_add(self, dmat, out: torch.Tensor,
+                           idxs: List[int]) -> torch.Tensor:
+        """Host sparse predict: add the trees `idxs` to `out`."""
+        for t, pos in self._sparse_leaf_ids(dmat, idxs):
+            tree = self.trees[t]
+            w = self._tw(t)
+            if tree.leaf_values is not None:  # vector leaves
+                out += w * torch.as_tensor(
+                    tree.leaf_values[:tree.n_nodes][pos], device=out.device)
+            else:
+                vals = tree.split_cond[:tree.n_nodes][pos]
+                out[:, self.tree_info[t]] += w * torch.as_tensor(
+                    vals, device=out.device)
         return out
 
     def _predict_margin_extmem(self, dmat, out: torch.Tensor,
@@ -1061,6 +1079,19 @@ class Booster:
         """Leaf node id of every row in trees [lo, hi): int32 [n, hi-lo]."""
         from .extmem import ExtMemQuantileDMatrix
         extmem = isinstance(data, ExtMemQuantileDMatrix)
+        sparse = getattr(data, "_sparse_data", None) is not None
+        if sparse and self.device.type == "cuda" and hi > lo:
+            from .backend.gpu import predict_margin_csr_gpu
+            leaf = torch.empty((data.num_row(), hi - lo),
+                               dtype=torch.int32, device=self.device)
+            predict_margin_csr_gpu(self, data, None, lo, hi, out_leaf=leaf)
+            return leaf.cpu().numpy()
+        if sparse:  # host walk on the used columns
+            ids = [pos for _, pos in
+                   self._sparse_leaf_ids(data, list(range(lo, hi)))]
+            if not ids:
+                return np.zeros((data.num_row(), 0), np.int32)
+            return np.stack(ids, axis=1)
         if self.device.type == "cuda" and hi > lo:
             from .backend.gpu import predict_margin_q_gpu, predict_q_supported
             train_cats = getattr(self, "cat_categories_", None)
@@ -1072,8 +1103,8 @@ class Booster:
                                    dtype=torch.int32, device=self.device)
                 predict_margin_q_gpu(self, data, None, lo, hi, out_leaf=leaf)
                 return leaf.cpu().numpy()
-        # host walk: CPU boosters, sparse CSR, re-aligned categorical
-        # frames and int32-bin pages
+        # host walk: CPU boosters, re-aligned categorical frames and
+        # int32-bin pages
         if extmem:
             pages = []
             for pi in range(len(data.pages)):

@@ -45,6 +45,10 @@ _SIGS = {
                     _p, _p, _i, _i, _p, _p, _p],
     "gbt_predict_q": [_p, _i, _i64, _i, _f, _i, _p, _p, _p, _p, _p, _p, _p,
                       _p, _i, _i, _p, _p, _p],
+    # indptr, indices, values, n_rows, n_features, forest (7 pointers),
+    # n_trees, n_groups, out_margin, out_leaf, force_search, grid_cap
+    "gbt_predict_csr": [_p, _p, _p, _i64, _i, _p, _p, _p, _p, _p, _p, _p,
+                        _i, _i, _p, _p, _i, _i, _p],
     "gbt_leaf_partition": [_p, _p, _i, _p, _p, _p],
     "gbt_leaf_decide": [_p, _p, _i, _p, _p, _i64, _p, _p, _i, _p, _p, _p,
                         _p, _p, _p, _p],

@@ -9,7 +9,8 @@ SRC = os.path.join(HERE, "cpp")
 OUT = os.path.join(HERE, "libgbt_hip.so")
 
 SOURCES = ["hist.hip", "partition.hip", "evaluate.hip", "compress.hip",
-           "predict.hip", "predict_bins.hip", "shap.hip", "shap_paths.hip", "shap_ix.hip",
+           "predict.hip", "predict_bins.hip", "predict_csr.hip", "shap.hip",
+           "shap_paths.hip", "shap_ix.hip",
            "driver.hip", "csr.hip", "gpair.hip", "mt_evaluate.hip",
            "cpu_hist.cpp"]
 
@@ -19,7 +20,8 @@ def build(force: bool = False) -> str:
                if os.path.exists(os.path.join(SRC, s))]
     if not force and os.path.exists(OUT):
         newest = max(os.path.getmtime(s) for s in sources +
-                     [os.path.join(SRC, "gbt_kernels.h")])
+                     [os.path.join(SRC, h)
+                      for h in ("gbt_kernels.h", "predict_walk.h")])
         if os.path.getmtime(OUT) >= newest:
             return OUT
     hipcc = os.environ.get("HIPCC", "hipcc")

@@ -141,6 +141,23 @@ void gbt_predict_q(const void* X, int kind, int64_t n_rows, int n_features,
                    int32_t* out_leaf,            // [n_rows, n_trees] or null
                    hipStream_t stream);
 
+// Packed-node predictor on sparse CSR rows (predict_csr.hip): forest
+// arrays as for gbt_predict_q, raw-float kind.  Column indices are sorted
+// within a row; an absent feature or a stored NaN is missing.
+// force_search: 0 = LDS-dense rows when they fit the budget (64 columns),
+// nonzero = always binary search.
+// grid_cap: most blocks to launch, 0 = gbt_predict_q's cap.
+void gbt_predict_csr(const int64_t* indptr,   // [n_rows+1]
+                     const int32_t* indices,  // [nnz]
+                     const float* values,     // [nnz]
+                     int64_t n_rows, int n_features, const void* nodes,
+                     const int32_t* tree_offsets, const int32_t* cat_offsets,
+                     const uint32_t* cat_bits, const int32_t* tree_group,
+                     const int32_t* vec_offset, const float* leaf_vec,
+                     int n_trees, int n_groups, float* out_margin,
+                     int32_t* out_leaf, int force_search, int grid_cap,
+                     hipStream_t stream);
+
 void gbt_leaf_decide(const uint8_t* gidx8, const uint16_t* gidx16,
                      int n_features,
                      const uint8_t* gidx8_col, const uint16_t* gidx16_col,

@@ -20,19 +20,50 @@
 // tree_group[t] == -1 adds the K-vector at leaf_vec[(vec_offset[t] +
 // nid) * K].  For every (row, k) the adds happen in tree order with
 // plain fp32 adds, so the result is bit-identical to the host loops.
+// The walk itself is predict_walk.h (shared with predict_csr.hip); this
+// file supplies the dense row loaders.
 #include "gbt_kernels.h"
+#include "predict_walk.h"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace {
 
-constexpr uint32_t kDefaultLeft = 1u << 31;
-constexpr uint32_t kIsCat = 1u << 30;
-constexpr uint32_t kFeatMask = kIsCat - 1u;
+using gbt_walk::kDefaultGridCap;
+using gbt_walk::WalkForest;
 
-// KMAX: 1 = single output column in a register, 4 = up to four columns
-// in registers (statically indexed), 0 = accumulate in global memory.
+// One dense row of raw floats.
+struct RawRow {
+  using Value = float;
+  const float* x;
+  float missing_value;
+  int missing_is_nan;
+  __device__ bool Get(int f, float* v) const {
+    *v = x[f];
+    return !(missing_is_nan ? isnan(*v)
+                            : (*v == missing_value || isnan(*v)));
+  }
+  __device__ static int Category(float v) { return (int)v; }
+  __device__ static bool Less(float v, int w) {
+    return v < __int_as_float(w);
+  }
+};
+
+// One dense row of local bin ids (u8 / u16).
+template <typename T>
+struct BinRow {
+  using Value = uint32_t;
+  const T* x;
+  const int32_t* n_bins;
+  __device__ bool Get(int f, uint32_t* v) const {
+    *v = (uint32_t)x[f];
+    return *v < (uint32_t)n_bins[f];
+  }
+  __device__ static int Category(uint32_t v) { return (int)v; }
+  __device__ static bool Less(uint32_t v, int w) { return v <= (uint32_t)w; }
+};
+
 template <typename T, int KMAX>
 __global__ __launch_bounds__(256) void PredictQKernel(
     const T* __restrict__ X, int64_t n_rows, int n_features,
@@ -45,103 +76,20 @@ __global__ __launch_bounds__(256) void PredictQKernel(
     const int32_t* __restrict__ vec_offset,
     const float* __restrict__ leaf_vec, int n_trees, int n_groups,
     float* __restrict__ out_margin, int32_t* __restrict__ out_leaf) {
-  constexpr bool kRaw = std::is_same<T, float>::value;
-  constexpr int kRegs = KMAX > 0 ? KMAX : 1;
   const int64_t row0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (int64_t row = row0; row < n_rows;
        row += (int64_t)gridDim.x * blockDim.x) {
     const T* xrow = X + row * n_features;
-    float* orow =
-        out_margin != nullptr ? out_margin + row * n_groups : nullptr;
-    float acc[kRegs];
-    if (KMAX > 0 && orow != nullptr) {
-#pragma unroll
-      for (int k = 0; k < kRegs; ++k) {
-        acc[k] = k < n_groups ? orow[k] : 0.0f;
-      }
-    }
-    for (int t = 0; t < n_trees; ++t) {
-      const int base = tree_offsets[t];
-      int nid = 0;
-      int4 nd = nodes[base];
-      while (nd.x != -1) {
-        const uint32_t fw = (uint32_t)nd.z;
-        const int f = (int)(fw & kFeatMask);
-        bool missing;
-        float v = 0.0f;
-        uint32_t local = 0;
-        if constexpr (kRaw) {
-          v = xrow[f];
-          missing =
-              missing_is_nan ? isnan(v) : (v == missing_value || isnan(v));
-        } else {
-          local = (uint32_t)xrow[f];
-          missing = local >= (uint32_t)n_bins[f];
-        }
-        bool go_left;
-        if (missing) {
-          go_left = (fw & kDefaultLeft) != 0;
-        } else if (fw & kIsCat) {
-          int c;
-          if constexpr (kRaw) {
-            c = (int)v;
-          } else {
-            c = (int)local;
-          }
-          const int w0 = cat_offsets[base + nid];
-          const int nw = cat_offsets[base + nid + 1] - w0;
-          bool in_set = false;
-          if (c >= 0 && (c >> 5) < nw) {
-            in_set = (cat_bits[w0 + (c >> 5)] >> (c & 31)) & 1u;
-          }
-          go_left = !in_set;  // stored set goes RIGHT
-        } else {
-          if constexpr (kRaw) {
-            go_left = v < __int_as_float(nd.w);
-          } else {
-            go_left = local <= (uint32_t)nd.w;
-          }
-        }
-        nid = go_left ? nd.x : nd.y;
-        nd = nodes[base + nid];
-      }
-      if (out_leaf != nullptr) {
-        out_leaf[row * n_trees + t] = nid;
-      }
-      if (orow == nullptr) {
-        continue;
-      }
-      const int g = tree_group[t];
-      if (g >= 0) {
-        const float leaf = __int_as_float(nd.w);
-        if (KMAX > 0) {
-#pragma unroll
-          for (int k = 0; k < kRegs; ++k) {
-            if (k == g) acc[k] += leaf;
-          }
-        } else {
-          orow[g] += leaf;
-        }
-      } else {
-        const float* lv =
-            leaf_vec + ((int64_t)vec_offset[t] + nid) * n_groups;
-        if (KMAX > 0) {
-#pragma unroll
-          for (int k = 0; k < kRegs; ++k) {
-            if (k < n_groups) acc[k] += lv[k];
-          }
-        } else {
-          for (int k = 0; k < n_groups; ++k) {
-            orow[k] += lv[k];
-          }
-        }
-      }
-    }
-    if (KMAX > 0 && orow != nullptr) {
-#pragma unroll
-      for (int k = 0; k < kRegs; ++k) {
-        if (k < n_groups) orow[k] = acc[k];
-      }
+    if constexpr (std::is_same<T, float>::value) {
+      const RawRow rd{xrow, missing_value, missing_is_nan};
+      WalkForest<KMAX>(rd, row, nodes, tree_offsets, cat_offsets, cat_bits,
+                       tree_group, vec_offset, leaf_vec, n_trees, n_groups,
+                       out_margin, out_leaf);
+    } else {
+      const BinRow<T> rd{xrow, n_bins};
+      WalkForest<KMAX>(rd, row, nodes, tree_offsets, cat_offsets, cat_bits,
+                       tree_group, vec_offset, leaf_vec, n_trees, n_groups,
+                       out_margin, out_leaf);
     }
   }
 }
@@ -155,7 +103,7 @@ void Launch(const void* X, int64_t n_rows, int n_features,
             const float* leaf_vec, int n_trees, int n_groups,
             float* out_margin, int32_t* out_leaf, hipStream_t stream) {
   const int64_t blocks64 = (n_rows + 255) / 256;
-  const dim3 grid((unsigned)std::min<int64_t>(blocks64, 2048 * 4));
+  const dim3 grid((unsigned)std::min<int64_t>(blocks64, kDefaultGridCap));
   const dim3 block(256);
   const T* Xt = static_cast<const T*>(X);
   const int4* nd = static_cast<const int4*>(nodes);
