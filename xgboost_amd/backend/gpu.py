@@ -858,7 +858,8 @@ def shap_gpu(booster, dmat, lo: int, hi: int, phi: np.ndarray) -> np.ndarray:
     max_depth = max((t.max_depth() for t in booster.trees[lo:hi]), default=0)
     n, n_groups, n_cols = phi.shape
     if max_depth > 16 or n_cols > 129:
-        raise ImportError("GPU SHAP limits exceeded; falling back to CPU")
+        raise ShapDeviceLimit(
+            "GPU SHAP limits exceeded; falling back to CPU")
     device = booster.device
     fa = _ForestArrays(booster, lo, hi, device)
     dd = dmat.device_data() if hasattr(dmat, 'device_data') else None
@@ -868,10 +869,32 @@ def shap_gpu(booster, dmat, lo: int, hi: int, phi: np.ndarray) -> np.ndarray:
         dtype=torch.float64, device=device)
     out = torch.from_numpy(
         np.ascontiguousarray(phi, np.float32)).to(device)
-    missing = dmat.missing
+    _launch_shap_dfs(fa, X, n, dmat.num_col(), dmat.missing, expected,
+                     n_groups, n_cols, out)
+    res = out.cpu().numpy()
+    if n_groups == 1:
+        return res[:, 0, :]
+    return res
+
+
+class ShapDeviceLimit(ImportError):
+    """The forest is outside what the SHAP kernels handle (categorical
+    splits past the DFS kernel's caps, a path of more than 16 features,
+    no room for one row): the caller runs the exact host recursion.  An
+    ImportError so that the dense entry points keep catching it."""
+
+
+def _launch_shap_dfs(fa: _ForestArrays, X: torch.Tensor, n: int,
+                     n_features: int, missing: float,
+                     expected: torch.Tensor, n_groups: int, n_cols: int,
+                     out: torch.Tensor) -> None:
+    """DFS kernel (shap.hip) on row-major X [n, n_features]; adds into
+    the float32 out [n, n_groups, n_cols]."""
+    from .. import ops as hip_ops
+    lib = hip_ops.load()
     missing_is_nan = 1 if np.isnan(missing) else 0
     lib.gbt_shap(
-        hip_ops.ptr(X), n, dmat.num_col(),
+        hip_ops.ptr(X), n, n_features,
         float(0.0 if missing_is_nan else missing), missing_is_nan,
         hip_ops.ptr(fa.tree_offsets), hip_ops.ptr(fa.left),
         hip_ops.ptr(fa.right), hip_ops.ptr(fa.split_index),
@@ -880,24 +903,86 @@ def shap_gpu(booster, dmat, lo: int, hi: int, phi: np.ndarray) -> np.ndarray:
         hip_ops.ptr(fa.cat_bits), hip_ops.ptr(fa.sum_hess),
         hip_ops.ptr(fa.tree_group), fa.n_trees, n_groups, n_cols,
         hip_ops.ptr(expected), hip_ops.ptr(out), hip_ops.stream())
-    res = out.cpu().numpy()
-    if n_groups == 1:
-        return res[:, 0, :]
+
+
+class _PathTable:
+    """Device copy of build_path_table's arrays for trees [lo, hi).
+    With `col_map` the element features are compact column ids."""
+
+    def __init__(self, booster, lo: int, hi: int, device, col_map=None):
+        from ..shap_paths import build_path_table
+        pp, pg, ef, elo, ehi, emiss, ez, pv, bias = build_path_table(
+            booster.trees[lo:hi], booster.tree_info[lo:hi])
+        self.max_elems = int(np.diff(pp).max()) if len(pg) else 0
+        if self.max_elems > 16:
+            raise ShapDeviceLimit("GPU SHAP path length > 16; CPU fallback")
+        if col_map is not None:
+            ef = col_map[ef].astype(np.int32)
+        self.n_paths = len(pg)
+        self.bias = bias
+        rz = np.where(ez > 0, 1.0 / np.maximum(ez, 1e-300), 0.0)
+        self.t = {}
+        for name, arr in (("pp", pp), ("pg", pg), ("ef", ef), ("elo", elo),
+                          ("ehi", ehi), ("emiss", emiss), ("ez", ez),
+                          ("rz", rz), ("pv", pv)):
+            self.t[name] = torch.from_numpy(
+                np.ascontiguousarray(arr)).to(device)
+
+    def args(self):
+        from .. import ops as hip_ops
+        t = self.t
+        return (hip_ops.ptr(t["pp"]), hip_ops.ptr(t["pg"]),
+                hip_ops.ptr(t["ef"]), hip_ops.ptr(t["elo"]),
+                hip_ops.ptr(t["ehi"]), hip_ops.ptr(t["emiss"]),
+                hip_ops.ptr(t["ez"]), hip_ops.ptr(t["rz"]),
+                hip_ops.ptr(t["pv"]), self.n_paths)
+
+
+def _launch_shap_paths(tab: _PathTable, Xt: torch.Tensor, n: int,
+                       n_features: int, missing: float, n_groups: int,
+                       n_cols: int, out: torch.Tensor) -> None:
+    """Path kernel on feature-major Xt [n_features, n]; adds into the
+    float64 out [n_groups, n_cols, n]."""
+    from .. import ops as hip_ops
+    lib = hip_ops.load()
+    missing_is_nan = 1 if np.isnan(missing) else 0
+    fn = lib.gbt_shap_paths if tab.max_elems <= 8 else lib.gbt_shap_paths16
+    fn(hip_ops.ptr(Xt), n, n_features,
+       float(0.0 if missing_is_nan else missing), missing_is_nan,
+       *tab.args(), n_groups, n_cols, hip_ops.ptr(out), hip_ops.stream())
+
+
+def _launch_shap_ix(tab: _PathTable, Xt: torch.Tensor, n: int,
+                    n_features: int, missing: float, n_groups: int,
+                    n_cols: int, out: torch.Tensor) -> None:
+    """Interaction kernel on feature-major Xt; adds the off-diagonal
+    pair terms into the float64 out [n_groups, n_cols, n_cols, n]."""
+    from .. import ops as hip_ops
+    lib = hip_ops.load()
+    missing_is_nan = 1 if np.isnan(missing) else 0
+    lib.gbt_shap_ix(
+        hip_ops.ptr(Xt), n, n_features,
+        float(0.0 if missing_is_nan else missing), missing_is_nan,
+        *tab.args(), n_groups, n_cols, hip_ops.ptr(out), hip_ops.stream())
+
+
+def _complete_diagonal(cube: torch.Tensor, base: torch.Tensor) -> torch.Tensor:
+    """[n, g, C, C] float64 from the kernel's cube [g, C, C, n]: each
+    diagonal cell is the contribution `base` [n, g, C] minus the rest of
+    its row, like the CPU path."""
+    ix = cube.permute(3, 0, 1, 2)  # [n, g, C, C] view
+    off_sum = ix.sum(dim=-1) - torch.diagonal(ix, dim1=-2, dim2=-1)
+    diag = base - off_sum
+    res = ix.clone()
+    res.diagonal(dim1=-2, dim2=-1).copy_(diag)
     return res
 
 
 def _shap_gpu_paths(booster, dmat, lo: int, hi: int,
                     phi: np.ndarray) -> np.ndarray:
-    from .. import ops as hip_ops
-    from ..shap_paths import build_path_table
-    lib = hip_ops.load()
     n, n_groups, n_cols = phi.shape
     device = booster.device
-    pp, pg, ef, elo, ehi, emiss, ez, pv, bias = build_path_table(
-        booster.trees[lo:hi], booster.tree_info[lo:hi])
-    max_elems = int(np.diff(pp).max()) if len(pg) else 0
-    if max_elems > 16:
-        raise ImportError("GPU SHAP path length > 16; CPU fallback")
+    tab = _PathTable(booster, lo, hi, device)
     dd = dmat.device_data() if hasattr(dmat, "device_data") else None
     X = dd if dd is not None else torch.from_numpy(dmat.raw_data()).to(device)
     X = X.t().contiguous()  # [F, n]: coalesced per-feature gathers
@@ -905,24 +990,11 @@ def _shap_gpu_paths(booster, dmat, lo: int, hi: int,
     out = torch.from_numpy(
         np.ascontiguousarray(phi, np.float64)).to(device)
     for grp in range(n_groups):
-        out[:, grp, n_cols - 1] += float(bias[grp]) if grp < len(bias) else 0.0
+        out[:, grp, n_cols - 1] += (float(tab.bias[grp])
+                                    if grp < len(tab.bias) else 0.0)
     out = out.permute(1, 2, 0).contiguous()  # [groups, cols, n]
-    rz = np.where(ez > 0, 1.0 / np.maximum(ez, 1e-300), 0.0)
-    t = {}
-    for name, arr in (("pp", pp), ("pg", pg), ("ef", ef), ("elo", elo),
-                      ("ehi", ehi), ("emiss", emiss), ("ez", ez),
-                      ("rz", rz), ("pv", pv)):
-        t[name] = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
-    missing = dmat.missing
-    missing_is_nan = 1 if np.isnan(missing) else 0
-    fn = lib.gbt_shap_paths if max_elems <= 8 else lib.gbt_shap_paths16
-    fn(hip_ops.ptr(X), n, dmat.num_col(),
-       float(0.0 if missing_is_nan else missing), missing_is_nan,
-       hip_ops.ptr(t["pp"]), hip_ops.ptr(t["pg"]), hip_ops.ptr(t["ef"]),
-       hip_ops.ptr(t["elo"]), hip_ops.ptr(t["ehi"]),
-       hip_ops.ptr(t["emiss"]), hip_ops.ptr(t["ez"]), hip_ops.ptr(t["rz"]),
-       hip_ops.ptr(t["pv"]),
-       len(pg), n_groups, n_cols, hip_ops.ptr(out), hip_ops.stream())
+    _launch_shap_paths(tab, X, n, dmat.num_col(), dmat.missing, n_groups,
+                       n_cols, out)
     res = out.permute(2, 0, 1).contiguous().cpu().numpy()
     if n_groups == 1:
         return res[:, 0, :]
@@ -942,64 +1014,192 @@ def shap_interactions_gpu(booster, dmat, lo: int, hi: int,
     completed from the contribution vector like the CPU path."""
     from .. import ops as hip_ops
     from ..shap import shap_values
-    from ..shap_paths import build_path_table
     lib = hip_ops.load()
     if not hasattr(lib, "gbt_shap_ix"):
         raise ImportError("gbt_shap_ix kernel not built")
-    has_cat = any(
-        t.split_type[:t.n_nodes].any() for t in booster.trees[lo:hi]
-        if hasattr(t, "split_type"))
-    if has_cat:
-        raise ImportError("GPU SHAP interactions: categorical fallback")
+    if _has_categorical(booster, lo, hi):
+        raise ShapDeviceLimit("GPU SHAP interactions: categorical fallback")
     n = dmat.num_row()
     f = dmat.num_col()
     n_groups = booster.n_outputs
     C = f + 1
     device = booster.device
-    pp, pg, ef, elo, ehi, emiss, ez, pv, bias = build_path_table(
-        booster.trees[lo:hi], booster.tree_info[lo:hi])
-    m = np.diff(pp)
-    if len(m) and int(m.max()) > 16:
-        raise ImportError("GPU SHAP interactions: path length > 16")
+    tab = _PathTable(booster, lo, hi, device)
     out_bytes = n * n_groups * C * C * 8
     free, _total = torch.cuda.mem_get_info()
     if out_bytes > free - (2 << 30):
-        raise ImportError("GPU SHAP interactions: output exceeds HBM")
-    rz = np.where(ez > 0, 1.0 / np.maximum(ez, 1e-300), 0.0)
-    t = {}
-    for name, arr in (("pp", pp), ("pg", pg), ("ef", ef), ("elo", elo),
-                      ("ehi", ehi), ("emiss", emiss), ("ez", ez),
-                      ("rz", rz), ("pv", pv)):
-        t[name] = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+        raise ShapDeviceLimit("GPU SHAP interactions: output exceeds HBM")
     dd = dmat.device_data() if hasattr(dmat, "device_data") else None
     X = dd if dd is not None else torch.from_numpy(dmat.raw_data()).to(device)
     X = X.t().contiguous()  # [F, n] coalesced gathers
     out = torch.zeros((n_groups, C, C, n), dtype=torch.float64,
                       device=device)
-    missing = dmat.missing
-    missing_is_nan = 1 if np.isnan(missing) else 0
-    lib.gbt_shap_ix(
-        hip_ops.ptr(X), n, f, float(0.0 if missing_is_nan else missing),
-        missing_is_nan, hip_ops.ptr(t["pp"]), hip_ops.ptr(t["pg"]),
-        hip_ops.ptr(t["ef"]), hip_ops.ptr(t["elo"]), hip_ops.ptr(t["ehi"]),
-        hip_ops.ptr(t["emiss"]), hip_ops.ptr(t["ez"]), hip_ops.ptr(t["rz"]),
-        hip_ops.ptr(t["pv"]), len(pg), n_groups, C, hip_ops.ptr(out),
-        hip_ops.stream())
+    _launch_shap_ix(tab, X, n, f, dmat.missing, n_groups, C, out)
     # diagonal completion from the (GPU) contribution vector
     base = shap_values(booster, dmat, iteration_range)
     base_t = torch.as_tensor(np.ascontiguousarray(base, np.float64),
                              device=device)
     if n_groups == 1:
         base_t = base_t[:, None, :]
-    ix = out.permute(3, 0, 1, 2)  # [n, g, C, C] view
-    off_sum = ix.sum(dim=-1) - torch.diagonal(ix, dim1=-2, dim2=-1)
-    diag = base_t - off_sum
-    res = ix.clone()
-    res.diagonal(dim1=-2, dim2=-1).copy_(diag)
-    res = res.cpu().numpy()
+    res = _complete_diagonal(out, base_t).cpu().numpy()
     if n_groups == 1:
         return res[:, 0].astype(np.float32)
     return res.astype(np.float32)
+
+
+def _has_categorical(booster, lo: int, hi: int) -> bool:
+    return any(
+        t.split_type[:t.n_nodes].any() for t in booster.trees[lo:hi]
+        if hasattr(t, "split_type"))
+
+
+# -- SHAP on sparse CSR input (shap_csr.hip stages the kernels' input) ----
+
+# rows per chunk on the CSR routes; None sizes it from free device memory
+_SHAP_CSR_CHUNK_ROWS: Optional[int] = None
+
+
+def _shap_csr_chunk_rows(n: int, bytes_per_row: int) -> int:
+    if _SHAP_CSR_CHUNK_ROWS is not None:
+        return max(1, min(n, int(_SHAP_CSR_CHUNK_ROWS)))
+    free, _total = torch.cuda.mem_get_info()
+    rows = (free - (2 << 30)) // max(1, bytes_per_row)
+    if rows < 1:
+        raise ShapDeviceLimit("GPU SHAP on CSR: no room for one row")
+    return int(min(n, rows))
+
+
+def _gather_csr_columns(csr_dev, row_begin: int, col_map: torch.Tensor,
+                        tile: torch.Tensor) -> None:
+    """NaN-fill `tile` [U, rows] and write into it the stored entries of
+    the CSR rows [row_begin, row_begin + rows) whose column is used."""
+    from .. import ops as hip_ops
+    lib = hip_ops.load()
+    indptr, indices, values = csr_dev
+    n_used, rows = tile.shape
+    assert (indptr.dtype == torch.int64 and indices.dtype == torch.int32
+            and values.dtype == torch.float32
+            and col_map.dtype == torch.int32
+            and tile.dtype == torch.float32)
+    assert 0 <= row_begin and row_begin + rows <= indptr.shape[0] - 1
+    tile.fill_(float("nan"))
+    lib.gbt_csr_gather_columns(
+        hip_ops.ptr(indptr), hip_ops.ptr(indices), hip_ops.ptr(values),
+        int(row_begin), int(rows), hip_ops.ptr(col_map),
+        int(col_map.shape[0]), int(n_used), hip_ops.ptr(tile),
+        hip_ops.stream())
+
+
+class _ShapCsrPlan:
+    """What the CSR routes share: the compact path table or remapped
+    DFS forest, the device CSR and col_map, and the per-chunk staging of
+    the tile and of phi [G, U+1, rows] float64 (bias column preset)."""
+
+    def __init__(self, booster, dmat, lo, hi, used, col_map, want_ix):
+        from ..shap import _expected_value
+        assert int(col_map.max(initial=-1)) < len(used)
+        self.device = device = booster.device
+        self.n = dmat.num_row()
+        self.u = len(used)
+        self.g = booster.n_outputs
+        self.base = booster._base_margin_value()
+        self.fa = self.tab = None
+        if _has_categorical(booster, lo, hi):
+            depth = max((t.max_depth() for t in booster.trees[lo:hi]),
+                        default=0)
+            if want_ix or depth > 16 or self.u + 1 > 129:
+                raise ShapDeviceLimit(
+                    "GPU SHAP on CSR: categorical forest past the DFS "
+                    "kernel's limits")
+            self.fa = fa = _ForestArrays(booster, lo, hi, device)
+            cm = torch.from_numpy(col_map).to(device)
+            # leaves keep 0: their split_index is never a column
+            fa.split_index = torch.where(
+                fa.left >= 0,
+                cm[fa.split_index.long().clamp(0, len(col_map) - 1)],
+                torch.zeros_like(cm[:1])).contiguous()
+            self.expected = torch.tensor(
+                [_expected_value(booster.trees[t]) for t in range(lo, hi)],
+                dtype=torch.float64, device=device)
+        else:
+            self.tab = _PathTable(booster, lo, hi, device, col_map)
+        self.csr = _device_csr(dmat, device)
+        self.col_map = torch.from_numpy(col_map).to(device)
+
+    def chunks(self, bytes_per_row: int):
+        if self.n == 0:
+            return
+        rows = _shap_csr_chunk_rows(self.n, bytes_per_row)
+        for r0 in range(0, self.n, rows):
+            yield r0, min(rows, self.n - r0)
+
+    def tile(self, r0: int, rows: int) -> torch.Tensor:
+        tile = torch.empty((self.u, rows), dtype=torch.float32,
+                           device=self.device)
+        if self.u:
+            _gather_csr_columns(self.csr, r0, self.col_map, tile)
+        return tile
+
+    def contribs(self, tile: torch.Tensor) -> torch.Tensor:
+        """float64 [G, U+1, rows] from the path kernel."""
+        rows = tile.shape[1]
+        phi = torch.zeros((self.g, self.u + 1, rows), dtype=torch.float64,
+                          device=self.device)
+        bias = self.tab.bias
+        for grp in range(self.g):
+            phi[grp, self.u] = self.base + (
+                float(bias[grp]) if grp < len(bias) else 0.0)
+        _launch_shap_paths(self.tab, tile, rows, self.u, float("nan"),
+                           self.g, self.u + 1, phi)
+        return phi
+
+
+def shap_csr_gpu(booster, dmat, lo: int, hi: int, used: np.ndarray,
+                 col_map: np.ndarray) -> np.ndarray:
+    """pred_contribs for a sparse CSR DMatrix, in the compact space of
+    the U used columns: float32 [n, groups, U+1] on the host, which the
+    caller expands to full width (expanding here would only make the
+    device-to-host copy F/U times larger).  Numeric forests run the path
+    kernel, categorical ones the DFS kernel on the transposed tile."""
+    plan = _ShapCsrPlan(booster, dmat, lo, hi, used, col_map, False)
+    n, u, g = plan.n, plan.u, plan.g
+    res = np.empty((n, g, u + 1), dtype=np.float32)
+    # tile + fp64 phi + its row-major float32 copy (+ the DFS transpose)
+    for r0, rows in plan.chunks(8 * u + 12 * g * (u + 1)):
+        tile = plan.tile(r0, rows)
+        if plan.tab is not None:
+            out = plan.contribs(tile).permute(2, 0, 1).to(
+                torch.float32, memory_format=torch.contiguous_format)
+        else:
+            out = torch.zeros((rows, g, u + 1), dtype=torch.float32,
+                              device=plan.device)
+            out[:, :, u] = plan.base
+            _launch_shap_dfs(plan.fa, tile.t().contiguous(), rows, u,
+                             float("nan"), plan.expected, g, u + 1, out)
+        res[r0:r0 + rows] = out.cpu().numpy()
+    return res
+
+
+def shap_interactions_csr_gpu(booster, dmat, lo: int, hi: int,
+                              used: np.ndarray,
+                              col_map: np.ndarray) -> np.ndarray:
+    """pred_interactions for a sparse CSR DMatrix in compact space:
+    float32 [n, groups, U+1, U+1] on the host.  The cube is
+    G*(U+1)^2*8 bytes a row instead of G*(F+1)^2*8."""
+    plan = _ShapCsrPlan(booster, dmat, lo, hi, used, col_map, True)
+    n, u, g = plan.n, plan.u, plan.g
+    C = u + 1
+    res = np.empty((n, g, C, C), dtype=np.float32)
+    # tile + phi + the cube, its completed clone and the float32 copy
+    for r0, rows in plan.chunks(4 * u + 8 * g * C + 20 * g * C * C):
+        tile = plan.tile(r0, rows)
+        base = plan.contribs(tile).permute(2, 0, 1)  # [rows, g, C] view
+        cube = torch.zeros((g, C, C, rows), dtype=torch.float64,
+                           device=plan.device)
+        _launch_shap_ix(plan.tab, tile, rows, u, float("nan"), g, C, cube)
+        out = _complete_diagonal(cube, base).to(torch.float32)
+        res[r0:r0 + rows] = out.cpu().numpy()
+    return res
 
 
 def _cached_forest(booster, lo: int, hi: int, device) -> _ForestArrays:

@@ -102,6 +102,9 @@ _SIGS = {
                          _p, _p, _p, _i64, _i, _i, _p, _p],
     "gbt_shap_ix": [_p, _i64, _i, _f, _i, _p, _p, _p, _p, _p, _p, _p, _p,
                     _p, _i64, _i, _i, _p, _p],
+    # indptr, indices, values, row_begin, n_rows_chunk, col_map,
+    # n_col_map, n_used, tile [n_used, n_rows_chunk]
+    "gbt_csr_gather_columns": [_p, _p, _p, _i64, _i64, _p, _i, _i, _p, _p],
     "gbt_hist_mt": [_p, _p, _i, _p, _i, _p, _p, _i, _p, _i, _i,
                     _p, _p, _i, _i, _p, _p],
 }

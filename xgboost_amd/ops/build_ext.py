@@ -10,7 +10,7 @@ OUT = os.path.join(HERE, "libgbt_hip.so")
 
 SOURCES = ["hist.hip", "partition.hip", "evaluate.hip", "compress.hip",
            "predict.hip", "predict_bins.hip", "predict_csr.hip", "shap.hip",
-           "shap_paths.hip", "shap_ix.hip",
+           "shap_paths.hip", "shap_ix.hip", "shap_csr.hip",
            "driver.hip", "csr.hip", "gpair.hip", "mt_evaluate.hip",
            "cpu_hist.cpp"]
 

@@ -10,6 +10,10 @@ approx_contribs) via the classic path-dependent TreeSHAP recursion
 Output convention matches xgboost: contribs shape [n, f+1] with the
 last column the bias (expected value incl. base_score); interactions
 [n, f+1, f+1]; multiclass adds a group axis [n, k, f+1].
+
+A sparse CSR DMatrix is explained in the compact space of the columns
+the forest splits on (absent entries and stored NaNs are missing) and
+expanded to full width at the end, on the CPU and on the GPU alike.
 """
 from __future__ import annotations
 
@@ -141,12 +145,29 @@ def _expected_value(tree: RegTree) -> float:
     return total / root_cover
 
 
+def _host_contribs(trees, groups, X: np.ndarray, phi: np.ndarray,
+                   missing: float, approx: bool) -> None:
+    """Add every tree's contributions to phi [n, groups, f + 1]."""
+    n, f = X.shape
+    for tree, k in zip(trees, groups):
+        phi[:, k, f] += _expected_value(tree)
+        if approx:
+            _saabas(tree, X, phi[:, k, :], missing)
+        else:
+            for i in range(n):
+                _tree_shap(tree, X[i], phi[i, k], missing)
+
+
 def shap_values(booster, dmat, iteration_range=(0, 0),
                 approx: bool = False) -> np.ndarray:
     lo, hi = booster._tree_range(iteration_range)
+    n_groups = booster.n_outputs
+    if _is_sparse(dmat):
+        compact, used = _csr_contribs(booster, dmat, lo, hi, approx)
+        phi = _expand_columns(compact, used, dmat.num_col(), 1)
+        return phi[:, 0, :] if n_groups == 1 else phi
     X = dmat.raw_data()
     n, f = X.shape
-    n_groups = booster.n_outputs
     phi = np.zeros((n, n_groups, f + 1), dtype=np.float64)
     phi[:, :, f] = booster._base_margin_value()
     if booster.device.type == "cuda" and not approx:
@@ -155,15 +176,8 @@ def shap_values(booster, dmat, iteration_range=(0, 0),
             return shap_gpu(booster, dmat, lo, hi, phi)
         except (ImportError, AttributeError):
             pass
-    for t in range(lo, hi):
-        tree = booster.trees[t]
-        k = booster.tree_info[t]
-        phi[:, k, f] += _expected_value(tree)
-        if approx:
-            _saabas(tree, X, phi[:, k, :], dmat.missing)
-        else:
-            for i in range(n):
-                _tree_shap(tree, X[i], phi[i, k], dmat.missing)
+    _host_contribs(booster.trees[lo:hi], booster.tree_info[lo:hi], X, phi,
+                   dmat.missing, approx)
     if n_groups == 1:
         return phi[:, 0, :].astype(np.float32)
     return phi.astype(np.float32)
@@ -193,6 +207,10 @@ def _saabas(tree: RegTree, X: np.ndarray, phi: np.ndarray,
 
 def shap_interactions(booster, dmat, iteration_range=(0, 0)) -> np.ndarray:
     lo, hi = booster._tree_range(iteration_range)
+    if _is_sparse(dmat):
+        compact, used = _csr_interactions(booster, dmat, lo, hi)
+        out = _expand_columns(compact, used, dmat.num_col(), 2)
+        return out[:, 0] if booster.n_outputs == 1 else out
     if booster.device.type == "cuda":
         try:
             from .backend.gpu import shap_interactions_gpu
@@ -201,15 +219,24 @@ def shap_interactions(booster, dmat, iteration_range=(0, 0)) -> np.ndarray:
         except (ImportError, AttributeError):
             pass  # categorical / deep-path forests: exact CPU fallback
     X = dmat.raw_data()
-    n, f = X.shape
     n_groups = booster.n_outputs
-    out = np.zeros((n, n_groups, f + 1, f + 1), dtype=np.float64)
     base = shap_values(booster, dmat, iteration_range).astype(np.float64)
     if n_groups == 1:
         base = base[:, None, :]
-    for t in range(lo, hi):
-        tree = booster.trees[t]
-        k = booster.tree_info[t]
+    out = _host_interactions(booster.trees[lo:hi], booster.tree_info[lo:hi],
+                             X, base, dmat.missing)
+    if n_groups == 1:
+        return out[:, 0].astype(np.float32)
+    return out.astype(np.float32)
+
+
+def _host_interactions(trees, groups, X: np.ndarray, base: np.ndarray,
+                       missing: float) -> np.ndarray:
+    """Interaction cube [n, groups, f + 1, f + 1] in fp64; the diagonal
+    is completed from the contributions `base` [n, groups, f + 1]."""
+    n, f = X.shape
+    out = np.zeros((n, base.shape[1], f + 1, f + 1), dtype=np.float64)
+    for tree, k in zip(trees, groups):
         used = sorted(set(int(tree.split_index[nid])
                           for nid in range(tree.n_nodes)
                           if not tree.is_leaf(nid)))
@@ -217,9 +244,9 @@ def shap_interactions(booster, dmat, iteration_range=(0, 0)) -> np.ndarray:
             phi_on = np.zeros((n, f + 1))
             phi_off = np.zeros((n, f + 1))
             for i in range(n):
-                _tree_shap(tree, X[i], phi_on[i], dmat.missing,
+                _tree_shap(tree, X[i], phi_on[i], missing,
                            condition=1, condition_feature=j)
-                _tree_shap(tree, X[i], phi_off[i], dmat.missing,
+                _tree_shap(tree, X[i], phi_off[i], missing,
                            condition=-1, condition_feature=j)
             diff = (phi_on - phi_off) / 2.0
             diff[:, j] = 0.0
@@ -228,6 +255,111 @@ def shap_interactions(booster, dmat, iteration_range=(0, 0)) -> np.ndarray:
     for i_ in range(f + 1):
         out[:, :, i_, i_] = base[:, :, i_] - (
             out[:, :, i_, :].sum(axis=-1) - out[:, :, i_, i_])
-    if n_groups == 1:
-        return out[:, 0].astype(np.float32)
-    return out.astype(np.float32)
+    return out
+
+
+# -- sparse CSR input: compact used-column space --------------------------
+
+def _is_sparse(dmat) -> bool:
+    return getattr(dmat, "_sparse_data", None) is not None
+
+
+def used_columns(trees, n_col: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(used, col_map) for a forest over an `n_col`-wide matrix: `used`
+    is the sorted array of distinct split features, `col_map[c]` the
+    compact id of column c, or -1.  Compact ids ascend with the feature,
+    so build_path_table keeps every path's element order under the remap
+    and the fp64 accumulations run in the order they run on dense input.
+    A split on a feature the matrix does not have has no output column
+    to explain it in and raises."""
+    feats = [t.split_index[:t.n_nodes][t.left[:t.n_nodes] != -1]
+             for t in trees]
+    used = (np.unique(np.concatenate(feats)).astype(np.int64) if feats
+            else np.zeros(0, np.int64))
+    if len(used) and (used[-1] >= n_col or used[0] < 0):
+        bad = int(used[-1]) if used[-1] >= n_col else int(used[0])
+        raise ValueError(
+            f"the model splits on feature {bad}, but the matrix has "
+            f"{n_col} columns: no output column can hold its contribution")
+    col_map = np.full(n_col, -1, dtype=np.int32)
+    col_map[used] = np.arange(len(used), dtype=np.int32)
+    return used, col_map
+
+
+class _RemappedTree:
+    """Read-only view of a RegTree whose split features are compact
+    ids; every other attribute is the tree's own."""
+
+    def __init__(self, tree: RegTree, col_map: np.ndarray):
+        self._tree = tree
+        n = tree.n_nodes
+        split_index = tree.split_index[:n].copy()
+        internal = tree.left[:n] != -1
+        split_index[internal] = col_map[split_index[internal]]
+        self.split_index = split_index
+
+    def __getattr__(self, name):
+        return getattr(self._tree, name)
+
+
+def _gather_used_columns(csr, used: np.ndarray) -> np.ndarray:
+    """[n, U] float32 of the used columns: NaN where the CSR stores
+    nothing, the stored value (a 0.0 too) where it does."""
+    X = np.full((csr.shape[0], len(used)), np.nan, dtype=np.float32)
+    if len(used):
+        sub = csr[:, used].tocoo()
+        X[sub.row, sub.col] = sub.data
+    return X
+
+
+def _expand_columns(compact: np.ndarray, used: np.ndarray, n_col: int,
+                    n_axes: int) -> np.ndarray:
+    """Compact [n, g, U+1] (n_axes=1) or [n, g, U+1, U+1] (n_axes=2) to
+    the full-width float32 output: exact 0.0 in every unused column, the
+    bias in the last one."""
+    if len(used) == n_col:  # every column is used: compact is full width
+        return np.ascontiguousarray(compact, dtype=np.float32)
+    n, g = compact.shape[:2]
+    dst = np.append(used, n_col).astype(np.int64)
+    out = np.zeros((n, g) + (n_col + 1,) * n_axes, dtype=np.float32)
+    if n_axes == 1:
+        out[:, :, dst] = compact
+    else:
+        out[:, :, dst[:, None], dst[None, :]] = compact
+    return out
+
+
+def _csr_contribs(booster, dmat, lo: int, hi: int, approx: bool):
+    """Compact float32 contributions [n, groups, U+1] and `used`."""
+    used, col_map = used_columns(booster.trees[lo:hi], dmat.num_col())
+    if booster.device.type == "cuda" and not approx:
+        from .backend import gpu
+        try:
+            return gpu.shap_csr_gpu(booster, dmat, lo, hi, used, col_map), used
+        except gpu.ShapDeviceLimit:
+            pass  # categorical past the DFS caps / deep paths: exact host
+    n, u = dmat.num_row(), len(used)
+    X = _gather_used_columns(dmat.sparse_data(), used)
+    phi = np.zeros((n, booster.n_outputs, u + 1), dtype=np.float64)
+    phi[:, :, u] = booster._base_margin_value()
+    trees = [_RemappedTree(t, col_map) for t in booster.trees[lo:hi]]
+    _host_contribs(trees, booster.tree_info[lo:hi], X, phi, np.nan, approx)
+    return phi.astype(np.float32), used
+
+
+def _csr_interactions(booster, dmat, lo: int, hi: int):
+    """Compact float32 interactions [n, groups, U+1, U+1] and `used`."""
+    used, col_map = used_columns(booster.trees[lo:hi], dmat.num_col())
+    if booster.device.type == "cuda":
+        from .backend import gpu
+        try:
+            return gpu.shap_interactions_csr_gpu(booster, dmat, lo, hi, used,
+                                                 col_map), used
+        except gpu.ShapDeviceLimit:
+            pass  # categorical / deep-path forests: exact host
+    base, _ = _csr_contribs(booster, dmat, lo, hi, False)
+    X = _gather_used_columns(dmat.sparse_data(), used)
+    trees = [_RemappedTree(t, col_map) for t in booster.trees[lo:hi]]
+    out = _host_interactions(trees, booster.tree_info[lo:hi], X,
+                             base.astype(np.float64), np.nan)
+    return out.astype(np.float32), used
