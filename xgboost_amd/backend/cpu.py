@@ -129,7 +129,9 @@ class CpuOps(SegmentedOpsMixin):
         self.gidx_global = qm.global_gidx()  # int64 [n, f], -1 missing
         self.n_bins = qm.cuts.total_bins
         self.lib = None
-        if use_native:
+        # the C kernels take u8 / u16 bin matrices only; an int32 matrix
+        # (a feature with more than 65535 local ids) stays on the torch path
+        if use_native and qm.gidx.dtype in (torch.uint8, torch.int16):
             try:
                 from .. import ops as hip_ops
                 lib = hip_ops.load()

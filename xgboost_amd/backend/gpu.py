@@ -25,6 +25,19 @@ from .cpu import GradQuantizer
 LDS_MAX_GROUP_BINS = 8192
 TARGET_HIST_TASKS = 2048  # fill 256 CUs x 8 blocks
 MIN_ROWS_PER_TASK = 1024
+# features whose metadata one multi-target histogram block stages in LDS
+# (GBT_HIST_MAX_F in ops/cpp/hist.hip: HistMtKernel has no unstaged path)
+HIST_MAX_GROUP_FEATURES = 1024
+
+
+def _check_bin_dtype(gidx: torch.Tensor) -> None:
+    """The HIP kernels read the bin matrix as uint8_t or uint16_t (i16
+    storage); anything wider would be silently reinterpreted."""
+    if gidx.dtype not in (torch.uint8, torch.int16):
+        raise ValueError(
+            f"GPU kernels take uint8 or 16-bit bin matrices, got "
+            f"{gidx.dtype}: a feature has more than 65535 local bin ids "
+            f"(lower max_bin or the category count, or train on the CPU)")
 
 
 def _chunk_tasks(segments: Sequence[Tuple[int, int]],
@@ -121,6 +134,7 @@ class GpuOps(SegmentedOpsMixin):
         self.hip = hip_ops
         self.qm = qm
         assert qm.gidx.is_cuda, "QuantizedMatrix must be on the GPU"
+        _check_bin_dtype(qm.gidx)
         self.device = qm.gidx.device
         cuts = qm.cuts
         self.n_bins = cuts.total_bins
@@ -185,6 +199,7 @@ class GpuOps(SegmentedOpsMixin):
     def swap_gidx(self, gidx: torch.Tensor) -> None:
         """Point the kernels at a different (streamed-in) quantized page
         with the same cuts (external-memory path)."""
+        _check_bin_dtype(gidx)
         g8 = gidx.dtype == torch.uint8
         self._gidx8 = gidx if g8 else None
         self._gidx16 = None if g8 else gidx
@@ -248,7 +263,8 @@ class GpuOps(SegmentedOpsMixin):
 
     def _mt_grouping(self, T: int):
         """Feature groups sized so T histograms fit the LDS budget
-        (reference MtHistKernel AllocateBlocks, histogram.cu:309)."""
+        (reference MtHistKernel AllocateBlocks, histogram.cu:309) and no
+        group has more features than the kernel stages metadata for."""
         cache = self.__dict__.setdefault("_mt_group_cache", {})
         if T in cache:
             return cache[T]
@@ -259,7 +275,8 @@ class GpuOps(SegmentedOpsMixin):
             return None
         groups_f, groups_b, acc = [0], [0], 0
         for f, w in enumerate(widths):
-            if acc + w > budget and acc > 0:
+            if acc > 0 and (acc + w > budget or
+                            f - groups_f[-1] >= HIST_MAX_GROUP_FEATURES):
                 groups_f.append(f)
                 groups_b.append(int(self.qm.cuts.ptrs[f]))
                 acc = 0

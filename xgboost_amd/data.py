@@ -87,6 +87,10 @@ class QuantizedMatrix:
         ptrs = torch.from_numpy(self.cuts.ptrs).to(self.gidx.device)
         n_bins = (ptrs[1:] - ptrs[:-1])
         g = self.gidx.long()
+        if self.gidx.dtype == torch.int16:
+            # i16 storage holds u16 ids (the kernels read uint16_t):
+            # undo the sign extension of local ids >= 32768
+            g = g & 0xFFFF
         missing = g >= n_bins.unsqueeze(0)
         g = g + ptrs[:-1].unsqueeze(0)
         g[missing] = -1
