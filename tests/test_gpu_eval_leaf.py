@@ -5,6 +5,10 @@ import numpy as np
 import pytest
 import torch
 
+import eval_cases as ec
+from eval_cases import F as _F, G_SCALE as _G_SCALE, H_SCALE as _H_SCALE
+from eval_cases import NB as _NB, PTRS as _PTRS, QS as _QS
+from eval_cases import hists as _hists
 from xgboost_amd.params import make_train_param
 from xgboost_amd.splits import evaluate_splits_np
 
@@ -13,68 +17,12 @@ pytestmark = pytest.mark.gpu
 # ---------------------------------------------------------------------------
 # evaluate: gbt_evaluate_masked vs gbt_evaluate_ref vs numpy
 
-# one wave's chunk is 64 bins and the block covers 256: widths on both
-# sides of each, a one- and a two-bin feature, and one far wider than the
-# block (the max_bin 1024 case)
-_WIDTHS = np.array([1, 2, 63, 64, 65, 128, 255, 256, 257, 1000])
-_PTRS = np.concatenate([[0], np.cumsum(_WIDTHS)]).astype(np.int32)
-_F = len(_WIDTHS)
-_NB = int(_PTRS[-1])
-_QS = float(1 << 30)
-# a bin holds up to a few thousand rows of gradients quantized to 2^30
-_BIN_MAX = 3000 * (1 << 30)
-_G_SCALE = _QS / 3.7
-_H_SCALE = _QS / 0.9
 _SENTINEL = -77
-
-_hist_cache = {}
-
-
-def _hists(k):
-    """-> (hist [k, n_bins, 2], parents [k, 2]) int64, built once per k.
-
-    Every feature of a node sums to the node's parent minus a missing
-    remainder, as real histograms do.  Even nodes have a remainder (h >=
-    0, g of either sign) that differs per feature; odd nodes have none,
-    so both missing directions tie at every bin.  Runs of empty bins give
-    consecutive equal gains.  Node 0 has one all-empty feature; the last
-    node (k >= 3) has h = 0 everywhere."""
-    if k in _hist_cache:
-        return _hist_cache[k]
-    rng = np.random.RandomState(100 + k)
-    hist = np.zeros((k, _NB, 2), np.int64)
-    hist[:, :, 0] = rng.randint(-_BIN_MAX, _BIN_MAX, (k, _NB))
-    hist[:, :, 1] = rng.randint(0, _BIN_MAX, (k, _NB))
-    for i in range(k):
-        for f in range(_F):
-            b0, b1 = int(_PTRS[f]), int(_PTRS[f + 1])
-            for _ in range(3):  # runs of empty bins
-                if b1 - b0 >= 8:
-                    s = rng.randint(b0, b1 - 4)
-                    hist[i, s:s + rng.randint(2, 40), :][: b1 - s] = 0
-    hist[0, _PTRS[6]:_PTRS[7], :] = 0  # an all-empty feature
-    parents = np.zeros((k, 2), np.int64)
-    for i in range(k):
-        tot = np.stack([hist[i, _PTRS[f]:_PTRS[f + 1]].sum(0)
-                        for f in range(_F)])          # [F, 2]
-        parents[i, 0] = tot[:, 0].max() + rng.randint(-_BIN_MAX, _BIN_MAX)
-        parents[i, 1] = tot[:, 1].max() + rng.randint(0, _BIN_MAX)
-        if i % 2 == 1:
-            # no missing remainder: top one bin of every feature up to the
-            # parent (h stays >= 0: the parent is above every total)
-            for f in range(_F):
-                b = rng.randint(_PTRS[f], _PTRS[f + 1])
-                hist[i, b] += parents[i] - tot[f]
-    if k >= 3:
-        hist[k - 1, :, 1] = 0
-        parents[k - 1, 1] = 0
-    _hist_cache[k] = (hist, parents)
-    return _hist_cache[k]
 
 
 def _launch(fn, hist, parents, k_launch, p, *, maxabs=None, scales=None,
             monotone=None, bounds=None, mask=None, mask_stride=0, cat=None,
-            k_dev=None):
+            k_dev=None, narrow_max=0):
     """One evaluate launch with sentinel-filled outputs -> numpy
     (gain bits, bin, dir, lsum)."""
     from xgboost_amd import ops
@@ -101,7 +49,7 @@ def _launch(fn, hist, parents, k_launch, p, *, maxabs=None, scales=None,
        p.max_delta_step, p.min_child_weight, ops.ptr(t_mono),
        ops.ptr(t_bounds), mask_stride, ops.ptr(t_mask), ops.ptr(t_cat),
        ops.ptr(gain), ops.ptr(bins), ops.ptr(dirs), ops.ptr(lsum),
-       ops.ptr(t_kdev), 0, ops.stream())
+       ops.ptr(t_kdev), narrow_max, ops.stream())
     best = torch.full((n, 6), _SENTINEL, dtype=torch.int64, device=dev)
     ops.load().gbt_select_best(ops.ptr(gain), ops.ptr(bins), ops.ptr(dirs),
                                ops.ptr(lsum), k_launch, _F, ops.ptr(best),
@@ -138,20 +86,7 @@ def _check(k, params=None, oracle=True, **kw):
         monotone=kw.get("monotone"),
         cat_mask=None if cat is None else cat.astype(bool),
         node_bounds=kw.get("bounds"))
-    best = new[4]
-    n_valid = 0
-    for i, e in enumerate(want):
-        if e.feature < 0:
-            assert best[i, 1] == -1 and best[i, 5] == -1, i
-            continue
-        n_valid += 1
-        assert int(best[i, 5]) == e.feature, (i, best[i], e)
-        assert int(best[i, 1]) == e.split_bin, (i, best[i], e)
-        assert bool(best[i, 2]) == e.default_left, (i, best[i], e)
-        assert int(best[i, 3]) == e.left_gq and int(best[i, 4]) == e.left_hq
-        assert best[i, 0:1].view(np.float64)[0] == pytest.approx(
-            e.gain, rel=1e-12)
-    assert n_valid >= (k + 1) // 2
+    ec.check_best_against_oracle(new[4], want, k)
     return new
 
 
@@ -179,25 +114,23 @@ def test_evaluate_matches_ref_and_oracle(k):
 
 def test_evaluate_monotone_with_bounds():
     k = 5
-    rng = np.random.RandomState(1)
-    mono = np.array([1, -1, 1, -1, 0, 1, -1, 0, 1, -1], np.int8)
-    lo = -np.abs(rng.randn(k)) * 2.0
-    bounds = np.stack([lo, lo + np.abs(rng.randn(k)) * 3.0], axis=1)
+    mono, bounds = ec.monotone_and_bounds(k)
     _check(k, monotone=mono, bounds=bounds)
 
 
 def test_evaluate_per_node_mask():
     k = 5
-    rng = np.random.RandomState(2)
-    mask = (rng.rand(k, _F) < 0.5).astype(np.uint8)
-    mask[:, 3] = 1
+    mask = ec.per_node_mask(k)
     gain, bins, *_ = _check(k, mask=mask, mask_stride=_F)
     assert np.all(bins[mask == 0] == -1)
     assert np.all(gain.view(np.float64)[mask == 0] == -np.inf)
 
 
+_BROADCAST_MASK = np.array([[1, 0, 1, 1, 0, 1, 0, 1, 1, 0]], np.uint8)
+
+
 def test_evaluate_broadcast_mask_row():
-    mask = np.array([[1, 0, 1, 1, 0, 1, 0, 1, 1, 0]], np.uint8)
+    mask = _BROADCAST_MASK
     gain, bins, *_ = _check(5, mask=mask, mask_stride=0)
     assert np.all(bins[:, mask[0] == 0] == -1)
 
@@ -211,8 +144,10 @@ def test_evaluate_categorical_feature():
 
 
 def test_evaluate_regularized():
-    _check(5, params={"reg_alpha": 0.3, "max_delta_step": 0.7,
-                      "min_child_weight": 2.5, "reg_lambda": 1.5})
+    _check(5, params=ec.REGULARIZED)
+
+
+_MAXABS = np.array([3.7, 0.9], np.float32)
 
 
 def test_evaluate_device_scales_match_host_scales():
@@ -221,7 +156,7 @@ def test_evaluate_device_scales_match_host_scales():
     k = 5
     hist, parents = _hists(k)
     p = make_train_param({"max_depth": 6})
-    maxabs = np.array([3.7, 0.9], np.float32)
+    maxabs = _MAXABS
     scales = tuple(_QS / float(m) for m in maxabs)
     dev_new = _launch(lib.gbt_evaluate_masked, hist, parents, k, p,
                       maxabs=maxabs, scales=(0.0, 0.0))
@@ -245,3 +180,130 @@ def test_evaluate_k_dev_leaves_later_slots_untouched():
     for a, b in zip(new, full):
         assert np.array_equal(a[:live], b[:live])
 
+
+# ---------------------------------------------------------------------------
+# narrow path: EvaluateNarrowKernel's slots vs the block kernel's
+
+
+def _narrow_cases():
+    mono, bounds = ec.monotone_and_bounds(5)
+    cat = np.zeros(_F, np.uint8)
+    cat[1] = cat[4] = 1  # a narrow (two-bin) one and a wide one
+    return {
+        "plain": (5, None, {}),
+        "regularized": (5, ec.REGULARIZED, {}),
+        "monotone_bounds": (5, None, dict(monotone=mono, bounds=bounds)),
+        "per_node_mask": (5, None, dict(mask=ec.per_node_mask(5),
+                                        mask_stride=_F)),
+        "broadcast_mask": (5, None, dict(mask=_BROADCAST_MASK,
+                                         mask_stride=0)),
+        "device_scales": (5, None, dict(maxabs=_MAXABS, scales=(0.0, 0.0))),
+        "categorical": (5, {"max_cat_to_onehot": 128}, dict(cat=cat)),
+        "k_dev": (130, None, dict(k_dev=77)),
+    }
+
+
+@pytest.mark.parametrize("narrow_max", [2, 64, 256])
+@pytest.mark.parametrize("case", list(_narrow_cases()))
+def test_evaluate_narrow_matches_block(case, narrow_max):
+    """With narrow_max = n the scalar kernel owns every non-categorical
+    feature of at most n bins (2, 4 and 8 of the ten); every output slot,
+    the sentinels in untouched ones included, equals narrow_max = 0."""
+    from xgboost_amd import ops
+    lib = ops.load()
+    k, params, kw = _narrow_cases()[case]
+    hist, parents = _hists(k)
+    p = make_train_param(dict({"max_depth": 6}, **(params or {})))
+    block = _launch(lib.gbt_evaluate_masked, hist, parents, k, p, **kw)
+    narrow = _launch(lib.gbt_evaluate_masked, hist, parents, k, p,
+                     narrow_max=narrow_max, **kw)
+    for name, a, b in zip(("gain bits", "bin", "dir", "lsum", "best"),
+                          narrow, block):
+        assert np.array_equal(a, b), name
+    live = kw.get("k_dev", k)
+    gain, bins, dirs, lsum, best = narrow
+    assert np.all(gain[live:] == _SENTINEL) and np.all(dirs[live:] == 200)
+    assert np.all(best[live:] == _SENTINEL)
+    if "mask" not in kw and "monotone" not in kw:
+        # the one-bin feature of an even node splits present from missing:
+        # the narrow kernel found it
+        assert bins[0, 0] == 0
+    if "cat" in kw:
+        # the flagged two-bin feature stays with the block kernel, which
+        # writes the whole record
+        assert np.all(bins[:, 1] != _SENTINEL) and np.all(dirs[:, 1] != 200)
+        assert np.all(lsum[:, 1] != _SENTINEL)
+    if "mask" in kw:
+        rows = np.broadcast_to(kw["mask"], (k, _F)) == 0
+        assert np.all(bins[rows] == -1) and np.all(dirs[rows] == 200)
+        assert np.all(lsum[rows] == _SENTINEL)
+
+
+# ---------------------------------------------------------------------------
+# select: gbt_select_best vs numpy argmax
+
+_SELECT_K = 4
+_select_cache = {}
+
+
+def _select_inputs(f):
+    """Gains from eight finite values (ties everywhere) with about a
+    quarter -inf; row 1 all -inf; row 2's maximum planted at f = 70 and
+    again at the last feature; random payload."""
+    if f in _select_cache:
+        return _select_cache[f]
+    k = _SELECT_K
+    rng = np.random.RandomState(7 + f)
+    values = np.array([-3.5, -1.0, 0.0, 0.125, 0.5, 1.0, 2.75, 9.0])
+    gain = values[rng.randint(0, 8, (k, f))]
+    gain[rng.rand(k, f) < 0.25] = -np.inf
+    gain[1] = -np.inf
+    if f > 70:
+        gain[2, 70] = gain[2, f - 1] = 11.0
+    bins = rng.randint(0, 1 << 20, (k, f)).astype(np.int32)
+    dirs = rng.randint(0, 2, (k, f)).astype(np.uint8)
+    lsum = rng.randint(-(1 << 50), 1 << 50, (k, f, 2)).astype(np.int64)
+    want = np.zeros((k, 6), np.int64)
+    for i in range(k):
+        if not np.isfinite(gain[i]).any():
+            want[i] = (0, -1, 0, 0, 0, -1)
+            continue
+        j = int(np.argmax(gain[i]))  # the first maximum
+        want[i] = (gain[i, j:j + 1].view(np.int64)[0], bins[i, j],
+                   dirs[i, j], lsum[i, j, 0], lsum[i, j, 1], j)
+    _select_cache[f] = (gain, bins, dirs, lsum, want)
+    return _select_cache[f]
+
+
+def _select(f, k_dev=None):
+    from xgboost_amd import ops
+    dev = torch.device("cuda")
+    gain, bins, dirs, lsum, want = _select_inputs(f)
+    t = [torch.from_numpy(a).to(dev) for a in (gain, bins, dirs, lsum)]
+    t_kdev = (None if k_dev is None else
+              torch.tensor([k_dev], dtype=torch.int32, device=dev))
+    best = torch.full((_SELECT_K, 6), _SENTINEL, dtype=torch.int64,
+                      device=dev)
+    ops.load().gbt_select_best(ops.ptr(t[0]), ops.ptr(t[1]), ops.ptr(t[2]),
+                               ops.ptr(t[3]), _SELECT_K, f, ops.ptr(best),
+                               ops.ptr(t_kdev), ops.stream())
+    torch.cuda.synchronize()
+    return best.cpu().numpy(), want
+
+
+# 4096 is the last width of the one-wave launch and 4097 the first of the
+# 1024-thread one; at 20001 every thread of the latter loops
+@pytest.mark.parametrize("f", [1, 63, 4096, 4097, 20001])
+def test_select_best_matches_numpy_argmax(f):
+    got, want = _select(f)
+    assert np.array_equal(got, want)
+    assert want[1, 5] == -1
+    if f > 70:
+        assert want[2, 5] == 70  # the lower index wins across waves
+
+
+@pytest.mark.parametrize("f", [63, 4097])
+def test_select_best_k_dev_leaves_later_rows_untouched(f):
+    got, want = _select(f, k_dev=2)
+    assert np.array_equal(got[:2], want[:2])
+    assert np.all(got[2:] == _SENTINEL)

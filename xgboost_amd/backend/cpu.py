@@ -21,7 +21,7 @@ import torch
 from .. import collective
 from ..data import QuantizedMatrix
 from ..params import TrainParam
-from ..splits import SplitEntry, evaluate_splits_np
+from ..splits import SplitEntry, evaluate_splits_np, feature_set_mask
 
 QSHIFT = 30  # fixed-point fraction bits; sums of 2^30-scaled int32 fit int64
 
@@ -250,16 +250,8 @@ class CpuOps(SegmentedOpsMixin):
                 if monotone is not None else None)
         bounds = (np.ascontiguousarray(node_bounds, np.float64)
                   if node_bounds is not None else None)
-        mask = None
-        if feature_sets is not None and any(
-                fs is not None for fs in feature_sets):
-            mask = np.zeros((k, f), np.uint8)
-            for i, fs in enumerate(feature_sets):
-                if fs is None:
-                    mask[i] = 1
-                else:
-                    mask[i, np.asarray(fs, np.int64)] = 1
-        out = np.zeros((k, 6), np.int64)
+        mask = feature_set_mask(feature_sets, k, f)
+        out =np.zeros((k, 6), np.int64)
         self.lib.gbt_evaluate_cpu(
             cp(h_np), k, self.n_bins, f, cp(self._cut_ptrs_np), cp(parents),
             quantizer.g_scale, quantizer.h_scale, param.reg_lambda,

@@ -17,7 +17,7 @@ import torch
 from .. import collective
 from ..data import QuantizedMatrix
 from ..params import TrainParam
-from ..splits import SplitEntry
+from ..splits import SplitEntry, feature_set_mask
 from .cpu import GradQuantizer
 
 # LDS budget for the histogram kernel: 8192 bins * 16 B = 128 KiB
@@ -336,14 +336,7 @@ class GpuOps(SegmentedOpsMixin):
                    if monotone is not None else None)
         bounds_np = (np.ascontiguousarray(node_bounds, np.float64)
                      if node_bounds is not None else None)
-        mask_np = None
-        if feature_sets is not None and any(fs is not None for fs in feature_sets):
-            mask_np = np.zeros((k, f), dtype=np.uint8)
-            for i, fs in enumerate(feature_sets):
-                if fs is None:
-                    mask_np[i] = 1
-                else:
-                    mask_np[i, np.asarray(fs, np.int64)] = 1
+        mask_np = feature_set_mask(feature_sets, k, f)
         # wide categorical features (cardinality > max_cat_to_onehot) use
         # sorted-partition splits, evaluated HOST-side with the SAME
         # routine as the CPU oracle (splits._sorted_cat_split) so GPU and
@@ -361,13 +354,13 @@ class GpuOps(SegmentedOpsMixin):
                 mask_np[:, wide_feats] = 0
         parents, mono_t, bounds_t, mask_t = self.stager.upload(
             [parents_np, mono_np, bounds_np, mask_np])
-        self.lib.gbt_evaluate(
+        self.lib.gbt_evaluate_masked(
             self.hip.ptr(hist), k, self.n_bins, f,
             self.hip.ptr(self.cut_ptrs), self.hip.ptr(parents), None,
             quantizer.g_scale, quantizer.h_scale,
             param.reg_lambda, param.reg_alpha, param.max_delta_step,
             param.min_child_weight, self.hip.ptr(mono_t),
-            self.hip.ptr(bounds_t), self.hip.ptr(mask_t),
+            self.hip.ptr(bounds_t), f, self.hip.ptr(mask_t),
             self.hip.ptr(self.cat_feature),
             self.hip.ptr(gain), self.hip.ptr(bins), self.hip.ptr(dirs),
             self.hip.ptr(lsum), None,

@@ -20,7 +20,7 @@ import torch
 
 from .backend.cpu import GradQuantizer
 from .params import TrainParam
-from .splits import SplitEntry, calc_weight
+from .splits import SplitEntry, calc_weight, feature_set_mask
 from .tree_model import RegTree
 
 
@@ -704,15 +704,8 @@ class MultiTargetGrower:
             g_scales, np.float64)).to(dev)
         hs_t = torch.from_numpy(np.ascontiguousarray(
             h_scales, np.float64)).to(dev)
-        mask_t = None
-        if fs is not None:
-            m = np.zeros((k, f), np.uint8)
-            for i, s in enumerate(fs):
-                if s is None:
-                    m[i] = 1
-                else:
-                    m[i, np.asarray(s, np.int64)] = 1
-            mask_t = torch.from_numpy(m).to(dev)
+        m = feature_set_mask(fs, k, f)
+        mask_t = None if m is None else torch.from_numpy(m).to(dev)
         gain = torch.empty((k, f), dtype=torch.float64, device=dev)
         bins = torch.empty((k, f), dtype=torch.int32, device=dev)
         dirs = torch.empty((k, f), dtype=torch.uint8, device=dev)

@@ -31,9 +31,7 @@ _SIGS = {
     "gbt_hist": [_p, _p, _i, _p, _p, _p, _i, _p, _i, _p, _p, _i, _i, _p, _i, _p, _p],
     "gbt_partition": [_p, _p, _i, _p, _p, _i64, _p, _p, _p, _i, _p, _p, _p,
                       _p, _p, _p, _p, _p],
-    "gbt_evaluate": [_p, _i, _i, _i, _p, _p, _p, _d, _d, _d, _d, _d, _d,
-                     _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
-    # gbt_evaluate plus mask_stride; _ref is the single-wave reference
+    # _ref is the single-wave reference behind the same arguments
     "gbt_evaluate_masked": [_p, _i, _i, _i, _p, _p, _p, _d, _d, _d, _d, _d,
                             _d, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i,
                             _p],

@@ -1,5 +1,6 @@
 """Build the HIP kernel library for gfx950 (in-tree, travels with the
 repo snapshot).  Invoked by __graft_entry__.build() and on demand."""
+import glob
 import os
 import subprocess
 import sys
@@ -20,8 +21,7 @@ def build(force: bool = False) -> str:
                if os.path.exists(os.path.join(SRC, s))]
     if not force and os.path.exists(OUT):
         newest = max(os.path.getmtime(s) for s in sources +
-                     [os.path.join(SRC, h)
-                      for h in ("gbt_kernels.h", "predict_walk.h")])
+                     glob.glob(os.path.join(SRC, "*.h")))
         if os.path.getmtime(OUT) >= newest:
             return OUT
     hipcc = os.environ.get("HIPCC", "hipcc")

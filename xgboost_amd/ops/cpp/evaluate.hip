@@ -8,91 +8,17 @@
 // gains in float64 with the exact operation order of the numpy oracle
 // (xgboost_amd/splits.py) so results match bit-for-bit.  The first form,
 // one wave64 walking a feature in 64-bin chunks, remains as the
-// reference entry point and for features wider than the block.
+// reference entry point and for features wider than the block.  The gain
+// arithmetic itself (TryCandidate) lives in split_gain.h.
 #include "gbt_kernels.h"
+#include "split_gain.h"
 
 #include <algorithm>
 
 namespace {
 
-struct Best {
-  double gain;
-  int bin;       // global bin id
-  int dir;       // 1 = missing-left
-  long long lg;  // left sums (quantized)
-  long long lh;
-};
-
-__device__ __forceinline__ bool Better(const Best& a, const Best& b) {
-  // match numpy: strictly-greater gain wins; ties keep (dir asc, bin asc)
-  if (a.gain != b.gain) return a.gain > b.gain;
-  if (a.dir != b.dir) return a.dir < b.dir;
-  return a.bin < b.bin;
-}
-
-__device__ __forceinline__ double ThresholdL1(double g, double alpha) {
-  if (alpha == 0.0) return g;
-  double s = (g > 0.0) ? 1.0 : ((g < 0.0) ? -1.0 : 0.0);
-  double m = fabs(g) - alpha;
-  if (m < 0.0) m = 0.0;
-  return s * m;
-}
-
-struct Params {
-  double lam, alpha, mds, mcw;
-  double lo, hi;  // node weight bounds
-};
-
-__device__ __forceinline__ double CalcWeight(double g, double h,
-                                             const Params& p) {
-  double w = -ThresholdL1(g, p.alpha) / (h + p.lam);
-  if (p.mds > 0.0) {
-    w = fmin(fmax(w, -p.mds), p.mds);
-  }
-  return w;
-}
-
-__device__ __forceinline__ double GainGivenWeight(double g, double h, double w,
-                                                  const Params& p) {
-  return -(2.0 * g * w + (h + p.lam) * (w * w));
-}
-
 __device__ __forceinline__ long long ShflUpLL(long long v, int delta) {
   return __shfl_up(v, delta, 64);
-}
-
-// One candidate split (bin b, missing direction dir, left sums glq/hlq)
-// of a node with sums pg/ph: scaling, CalcWeight, the bound clamp, the
-// validity test and the gain expression.  The single-wave routine and
-// the one-thread-per-bin kernel both call this, so both evaluate the
-// same fp64 expression tree and their results are bit-identical.
-__device__ __forceinline__ void TryCandidate(long long glq, long long hlq,
-                                             long long pg, long long ph,
-                                             double inv_g, double inv_h,
-                                             const Params& p, int mono,
-                                             double parent_gain, int b,
-                                             int dir, Best* best) {
-  const long long grq = pg - glq;
-  const long long hrq = ph - hlq;
-  const double gl = glq * inv_g;
-  const double hl = hlq * inv_h;
-  const double gr = grq * inv_g;
-  const double hr = hrq * inv_h;
-  double wl = CalcWeight(gl, hl, p);
-  double wr = CalcWeight(gr, hr, p);
-  wl = fmin(fmax(wl, p.lo), p.hi);
-  wr = fmin(fmax(wr, p.lo), p.hi);
-  // empty-side splits rejected via exact hessian counts; the
-  // last-bin + missing-right split (present vs absent) is valid
-  bool ok = (hl >= p.mcw) && (hr >= p.mcw) && hlq > 0 && hrq > 0;
-  if (mono > 0) ok = ok && (wl <= wr);
-  if (mono < 0) ok = ok && (wl >= wr);
-  if (ok) {
-    const double gain = GainGivenWeight(gl, hl, wl, p)
-                        + GainGivenWeight(gr, hr, wr, p) - parent_gain;
-    Best cand{gain, b, dir, glq, hlq};
-    if (isfinite(gain) && Better(cand, *best)) *best = cand;
-  }
 }
 
 // wave argmax reduce with the full tie key; lane 0 holds the result
@@ -109,7 +35,7 @@ __device__ __forceinline__ void WaveArgmax(Best* best) {
   }
 }
 
-// the launch arguments shared by EvaluateKernel and EvaluateRefKernel
+// the launch arguments shared by the three evaluate kernels
 struct EvalArgs {
   const int64_t* hist;
   int n_nodes, n_bins, n_features;
@@ -139,7 +65,7 @@ struct EvalArgs {
 
 // everything one (node, feature) evaluation needs besides the bins
 struct FeatCtx {
-  Params p;
+  SplitParams p;
   int mono;
   bool is_cat;
   int fb0, fb1;
@@ -149,9 +75,40 @@ struct FeatCtx {
   size_t out_idx;
 };
 
-// Fills *c for (node, f).  False = this launch writes nothing more to
-// the slot: the narrow kernel owns it, or the feature is masked (then
-// `writer` stores the no-split record).  Block-uniform.
+// Who writes a (node, feature) slot: the narrow kernel takes the numeric
+// features of at most narrow_max bins, the block kernel the rest.
+__device__ __forceinline__ bool NarrowOwns(const EvalArgs& a, int width,
+                                           bool is_cat) {
+  return a.narrow_max > 0 && width <= a.narrow_max && !is_cat;
+}
+
+// the dequantisation factors, from host scales or the device max-abs pair
+__device__ __forceinline__ void SetScales(const EvalArgs& a, FeatCtx* c) {
+  double g_scale = a.g_scale, h_scale = a.h_scale;
+  if (a.maxabs != nullptr) {
+    // identical derivation to the host/QuantizeKernel formula
+    g_scale = a.maxabs[0] > 0.f ? 1073741824.0 / (double)a.maxabs[0] : 1.0;
+    h_scale = a.maxabs[1] > 0.f ? 1073741824.0 / (double)a.maxabs[1] : 1.0;
+  }
+  c->inv_g = 1.0 / g_scale;
+  c->inv_h = 1.0 / h_scale;
+}
+
+// two fp64 divisions: only for a slot that has candidates to compare
+__device__ __forceinline__ void SetParentGain(FeatCtx* c) {
+  const double pw = CalcWeight(c->pg * c->inv_g, c->ph * c->inv_h, c->p);
+  c->parent_gain =
+      GainGivenWeight(c->pg * c->inv_g, c->ph * c->inv_h, pw, c->p);
+}
+
+// Claims the slot (node, f) for the narrow kernel (kNarrow) or a block
+// kernel and fills *c.  False = this kernel writes nothing more to the
+// slot: the other kernel owns it, or the feature is masked (then `writer`
+// stores gain and bin of the no-split record).  Uniform over the threads
+// that share a slot.  The narrow kernel sets its scales once per thread
+// and the parent gain only for a feature the node's rows have, so for it
+// both stay out of here.
+template <bool kNarrow>
 __device__ __forceinline__ bool SetupFeature(const EvalArgs& a, int node,
                                              int f, bool writer,
                                              FeatCtx* c) {
@@ -159,9 +116,7 @@ __device__ __forceinline__ bool SetupFeature(const EvalArgs& a, int node,
   c->fb0 = a.cut_ptrs[f];
   c->fb1 = a.cut_ptrs[f + 1];
   c->is_cat = a.cat_feature && a.cat_feature[f];
-  if (a.narrow_max > 0 && c->fb1 - c->fb0 <= a.narrow_max && !c->is_cat) {
-    return false;  // the narrow kernel writes this slot
-  }
+  if (NarrowOwns(a, c->fb1 - c->fb0, c->is_cat) != kNarrow) return false;
   if (a.feature_mask != nullptr &&
       a.feature_mask[(size_t)node * a.mask_stride + f] == 0) {
     if (writer) {
@@ -179,18 +134,11 @@ __device__ __forceinline__ bool SetupFeature(const EvalArgs& a, int node,
   c->mono = a.monotone ? (int)a.monotone[f] : 0;
   c->pg = a.parent_sums[2 * node];
   c->ph = a.parent_sums[2 * node + 1];
-  double g_scale = a.g_scale, h_scale = a.h_scale;
-  if (a.maxabs != nullptr) {
-    // identical derivation to the host/QuantizeKernel formula
-    g_scale = a.maxabs[0] > 0.f ? 1073741824.0 / (double)a.maxabs[0] : 1.0;
-    h_scale = a.maxabs[1] > 0.f ? 1073741824.0 / (double)a.maxabs[1] : 1.0;
-  }
-  c->inv_g = 1.0 / g_scale;
-  c->inv_h = 1.0 / h_scale;
   c->nh = a.hist + (size_t)node * a.n_bins * 2;
-  const double pw = CalcWeight(c->pg * c->inv_g, c->ph * c->inv_h, c->p);
-  c->parent_gain =
-      GainGivenWeight(c->pg * c->inv_g, c->ph * c->inv_h, pw, c->p);
+  if (!kNarrow) {
+    SetScales(a, c);
+    SetParentGain(c);
+  }
   return true;
 }
 
@@ -283,7 +231,7 @@ __global__ __launch_bounds__(64) void EvaluateRefKernel(EvalArgs a) {
   const int lane = threadIdx.x;
   for (int f = blockIdx.x; f < a.n_features; f += gridDim.x) {
     FeatCtx c;
-    if (!SetupFeature(a, node, f, lane == 0, &c)) continue;
+    if (!SetupFeature<false>(a, node, f, lane == 0, &c)) continue;
     EvaluateFeatureWave(a, c, lane);
   }
 }
@@ -312,7 +260,7 @@ __global__ __launch_bounds__(kEvalBlock) void EvaluateKernel(EvalArgs a) {
   const int wave = tid >> 6;
   for (int f = blockIdx.x; f < a.n_features; f += gridDim.x) {
     FeatCtx c;
-    if (!SetupFeature(a, node, f, tid == 0, &c)) continue;
+    if (!SetupFeature<false>(a, node, f, tid == 0, &c)) continue;
     const int width = c.fb1 - c.fb0;
     if (width > kEvalBlock) {
       // max_bin 512 / 1024: wider than the block, wave 0 walks it
@@ -410,218 +358,101 @@ __global__ __launch_bounds__(kEvalBlock) void EvaluateKernel(EvalArgs a) {
   }
 }
 
-// Second stage: per-node argmax over features -> packed [n_nodes, 6]
-// (gain bits, bin, dir, left_gq, left_hq, feature).  One wave per node;
-// tie rule matches numpy flat argmax: higher gain wins, ties -> lower
-// feature index (the per-feature stage already resolved bin/dir ties).
 // Scalar evaluation for NARROW numeric features (one-hot scale sparse
 // data: millions of 2-bin features).  One THREAD per (node, feature);
-// identical fp64 operation order and tie rules as the wave kernel, so
-// results are bit-identical — only the parallelization differs.
-__global__ __launch_bounds__(256) void EvaluateNarrowKernel(
-    const int64_t* __restrict__ hist, int n_nodes, int n_bins,
-    int n_features, const int32_t* __restrict__ cut_ptrs,
-    const int64_t* __restrict__ parent_sums,
-    const float* __restrict__ maxabs,
-    const int32_t* __restrict__ k_dev, int narrow_max,
-    double g_scale, double h_scale, double reg_lambda, double reg_alpha,
-    double max_delta_step, double min_child_weight,
-    const int8_t* __restrict__ monotone,
-    const double* __restrict__ node_bounds,
-    int mask_stride, const uint8_t* __restrict__ feature_mask,
-    const uint8_t* __restrict__ cat_feature, double* __restrict__ out_gain,
-    int32_t* __restrict__ out_bin, uint8_t* __restrict__ out_dir,
-    int64_t* __restrict__ out_lsum) {
-  if (maxabs != nullptr) {
-    g_scale = maxabs[0] > 0.f ? 1073741824.0 / (double)maxabs[0] : 1.0;
-    h_scale = maxabs[1] > 0.f ? 1073741824.0 / (double)maxabs[1] : 1.0;
-  }
-  const double inv_g = 1.0 / g_scale;
-  const double inv_h = 1.0 / h_scale;
-  const int kn = (k_dev != nullptr) ? *k_dev : n_nodes;
-  const long long total = (long long)kn * n_features;
+// the same TryCandidate and tie rule as the block kernel, so results are
+// bit-identical — only the parallelization differs.
+__global__ __launch_bounds__(256) void EvaluateNarrowKernel(EvalArgs a) {
+  FeatCtx c;
+  SetScales(a, &c);
+  const int kn = (a.k_dev != nullptr) ? *a.k_dev : a.n_nodes;
+  const long long total = (long long)kn * a.n_features;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
        idx < total; idx += stride) {
-    const int node = (int)(idx / n_features);
-    const int f = (int)(idx % n_features);
-    const int fb0 = cut_ptrs[f], fb1 = cut_ptrs[f + 1];
-    if (fb1 - fb0 > narrow_max) continue;           // wave kernel's
-    if (cat_feature != nullptr && cat_feature[f]) continue;  // slot
-    const size_t out_idx = (size_t)node * n_features + f;
-    if (feature_mask != nullptr &&
-        feature_mask[(size_t)node * mask_stride + f] == 0) {
-      out_gain[out_idx] = -INFINITY;
-      out_bin[out_idx] = -1;
-      continue;
-    }
-    Params p;
-    p.lam = reg_lambda;
-    p.alpha = reg_alpha;
-    p.mds = max_delta_step;
-    p.mcw = min_child_weight;
-    p.lo = node_bounds ? node_bounds[2 * node] : -INFINITY;
-    p.hi = node_bounds ? node_bounds[2 * node + 1] : INFINITY;
-    const int mono = monotone ? (int)monotone[f] : 0;
-    const long long pg = parent_sums[2 * node];
-    const long long ph = parent_sums[2 * node + 1];
-    const int64_t* nh = hist + (size_t)node * n_bins * 2;
+    const int node = (int)(idx / a.n_features);
+    const int f = (int)(idx % a.n_features);
+    if (!SetupFeature<true>(a, node, f, true, &c)) continue;
     long long fg = 0, fh = 0;
-    for (int b = fb0; b < fb1; ++b) {
-      fg += nh[2 * b];
-      fh += nh[2 * b + 1];
+    for (int b = c.fb0; b < c.fb1; ++b) {
+      fg += c.nh[2 * b];
+      fh += c.nh[2 * b + 1];
     }
+    Best best{-INFINITY, -1, 0, 0, 0};
     if (fh == 0 && fg == 0) {
       // feature absent from this node's rows: every candidate split is
       // empty-vs-all and fails the exact hessian-count validity — the
-      // common case for one-hot features in deep nodes
-      out_gain[out_idx] = -INFINITY;
-      out_bin[out_idx] = -1;
-      out_dir[out_idx] = 0;
-      out_lsum[2 * out_idx] = 0;
-      out_lsum[2 * out_idx + 1] = 0;
+      // common case for one-hot features in deep nodes, so it leaves
+      // before the parent gain's divisions
+      WriteBest(a, c.out_idx, best);
       continue;
     }
-    const long long miss_g = pg - fg;
-    const long long miss_h = ph - fh;
-    const double pw = CalcWeight(pg * inv_g, ph * inv_h, p);
-    const double parent_gain =
-        GainGivenWeight(pg * inv_g, ph * inv_h, pw, p);
-    Best best{-INFINITY, -1, 0, 0, 0};
+    const long long miss_g = c.pg - fg;
+    const long long miss_h = c.ph - fh;
+    SetParentGain(&c);
     for (int dir = 0; dir < 2; ++dir) {
-      const long long add_g = dir ? miss_g : 0;
-      const long long add_h = dir ? miss_h : 0;
-      long long sg = 0, sh = 0;
-      for (int b = fb0; b < fb1; ++b) {
-        sg += nh[2 * b];
-        sh += nh[2 * b + 1];
-        const long long glq = sg + add_g;
-        const long long hlq = sh + add_h;
-        const long long grq = pg - glq;
-        const long long hrq = ph - hlq;
-        const double gl = glq * inv_g;
-        const double hl = hlq * inv_h;
-        const double gr = grq * inv_g;
-        const double hr = hrq * inv_h;
-        double wl = CalcWeight(gl, hl, p);
-        double wr = CalcWeight(gr, hr, p);
-        wl = fmin(fmax(wl, p.lo), p.hi);
-        wr = fmin(fmax(wr, p.lo), p.hi);
-        bool ok = (hl >= p.mcw) && (hr >= p.mcw) && hlq > 0 && hrq > 0;
-        if (mono > 0) ok = ok && (wl <= wr);
-        if (mono < 0) ok = ok && (wl >= wr);
-        if (ok) {
-          const double gain = GainGivenWeight(gl, hl, wl, p)
-                              + GainGivenWeight(gr, hr, wr, p) - parent_gain;
-          Best cand{gain, b, dir, glq, hlq};
-          if (isfinite(gain) && Better(cand, best)) best = cand;
-        }
+      long long sg = dir ? miss_g : 0, sh = dir ? miss_h : 0;
+      for (int b = c.fb0; b < c.fb1; ++b) {
+        sg += c.nh[2 * b];
+        sh += c.nh[2 * b + 1];
+        TryCandidate(sg, sh, c.pg, c.ph, c.inv_g, c.inv_h, c.p, c.mono,
+                     c.parent_gain, b, dir, &best);
       }
     }
-    out_gain[out_idx] = best.gain;
-    out_bin[out_idx] = best.bin;
-    out_dir[out_idx] = (uint8_t)best.dir;
-    out_lsum[2 * out_idx] = best.lg;
-    out_lsum[2 * out_idx + 1] = best.lh;
+    WriteBest(a, c.out_idx, best);
   }
 }
 
-// Wide-feature-count argmax: 1024 threads per node with an LDS
-// cross-wave reduction (one 64-thread wave over 1e6 one-hot features
-// was 5.4 ms/launch on the Criteo shape).
-__global__ __launch_bounds__(1024) void SelectBestWideKernel(
+// Second stage: per-node argmax over features -> packed [n_nodes, 6]
+// (gain bits, bin, dir, left_gq, left_hq, feature).  One block per node;
+// tie rule matches numpy flat argmax: higher gain wins, ties -> lower
+// feature index (the per-feature stage already resolved bin/dir ties).
+// kBlock = 64 is one wave per node; kBlock = 1024 adds an LDS reduction
+// across its 16 waves for wide feature counts (one 64-thread wave over
+// 1e6 one-hot features was 5.4 ms/launch on the Criteo shape).
+template <int kBlock>
+__global__ __launch_bounds__(kBlock) void SelectBestKernel(
     const double* __restrict__ gain, const int32_t* __restrict__ bins,
     const uint8_t* __restrict__ dirs, const int64_t* __restrict__ lsum,
     int n_features, int64_t* __restrict__ out_best,
     const int32_t* __restrict__ k_dev) {
   const int node = blockIdx.x;
   if (k_dev != nullptr && node >= *k_dev) return;
-  const int lane = threadIdx.x & 63;
-  const int wave = (int)threadIdx.x >> 6;
   const size_t base = (size_t)node * n_features;
   double best_gain = -INFINITY;
   int best_f = -1;
-  for (int f = (int)threadIdx.x; f < n_features; f += (int)blockDim.x) {
+  for (int f = (int)threadIdx.x; f < n_features; f += kBlock) {
     const double gv = gain[base + f];
     if (gv > best_gain) {
       best_gain = gv;
       best_f = f;
     }
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    const double og = __shfl_down(best_gain, off, 64);
-    const int of = __shfl_down(best_f, off, 64);
+  auto take = [&](double og, int of) {
     if (of >= 0 && (best_f < 0 || og > best_gain ||
                     (og == best_gain && of < best_f))) {
       best_gain = og;
       best_f = of;
     }
+  };
+  for (int off = 32; off > 0; off >>= 1) {
+    const double og = __shfl_down(best_gain, off, 64);
+    const int of = __shfl_down(best_f, off, 64);
+    take(og, of);
   }
-  __shared__ double s_g[1024 / 64];
-  __shared__ int s_f[1024 / 64];
-  if (lane == 0) {
-    s_g[wave] = best_gain;
-    s_f[wave] = best_f;
+  if constexpr (kBlock > 64) {
+    __shared__ double s_g[kBlock / 64];
+    __shared__ int s_f[kBlock / 64];
+    if ((threadIdx.x & 63) == 0) {
+      s_g[threadIdx.x >> 6] = best_gain;
+      s_f[threadIdx.x >> 6] = best_f;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int w = 1; w < kBlock / 64; ++w) take(s_g[w], s_f[w]);
+    }
   }
-  __syncthreads();
   if (threadIdx.x == 0) {
-    for (int w2 = 1; w2 < (int)blockDim.x / 64; ++w2) {
-      const double og = s_g[w2];
-      const int of = s_f[w2];
-      if (of >= 0 && (best_f < 0 || og > best_gain ||
-                      (og == best_gain && of < best_f))) {
-        best_gain = og;
-        best_f = of;
-      }
-    }
-    int64_t* out = out_best + (size_t)node * 6;
-    if (best_f < 0 || !isfinite(best_gain)) {
-      out[0] = 0;
-      out[1] = -1;
-      out[2] = 0;
-      out[3] = 0;
-      out[4] = 0;
-      out[5] = -1;
-    } else {
-      const size_t idx = base + best_f;
-      out[0] = __double_as_longlong(best_gain);
-      out[1] = bins[idx];
-      out[2] = dirs[idx];
-      out[3] = lsum[2 * idx];
-      out[4] = lsum[2 * idx + 1];
-      out[5] = best_f;
-    }
-  }
-}
-
-__global__ __launch_bounds__(64) void SelectBestKernel(
-    const double* __restrict__ gain, const int32_t* __restrict__ bins,
-    const uint8_t* __restrict__ dirs, const int64_t* __restrict__ lsum,
-    int n_features, int64_t* __restrict__ out_best,
-    const int32_t* __restrict__ k_dev) {
-  const int node = blockIdx.x;
-  if (k_dev != nullptr && node >= *k_dev) return;
-  const int lane = threadIdx.x;
-  const size_t base = (size_t)node * n_features;
-  double best_gain = -INFINITY;
-  int best_f = -1;
-  for (int f = lane; f < n_features; f += 64) {
-    const double gv = gain[base + f];
-    if (gv > best_gain) {
-      best_gain = gv;
-      best_f = f;
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const double og = __shfl_down(best_gain, off, 64);
-    const int of = __shfl_down(best_f, off, 64);
-    if (of >= 0 && (best_f < 0 || og > best_gain ||
-                    (og == best_gain && of < best_f))) {
-      best_gain = og;
-      best_f = of;
-    }
-  }
-  if (lane == 0) {
     int64_t* out = out_best + (size_t)node * 6;
     if (best_f < 0 || !isfinite(best_gain)) {
       out[0] = 0;
@@ -646,33 +477,15 @@ extern "C" void gbt_select_best(const double* gain, const int32_t* bins,
                                 const uint8_t* dirs, const int64_t* lsum,
                                 int n_nodes, int n_features,
                                 int64_t* out_best, const int32_t* k_dev,
-                                 hipStream_t stream) {
+                                hipStream_t stream) {
   if (n_features > 4096) {
-    hipLaunchKernelGGL(SelectBestWideKernel, dim3(n_nodes), dim3(1024), 0,
+    hipLaunchKernelGGL(SelectBestKernel<1024>, dim3(n_nodes), dim3(1024), 0,
                        stream, gain, bins, dirs, lsum, n_features, out_best,
                        k_dev);
     return;
   }
-  hipLaunchKernelGGL(SelectBestKernel, dim3(n_nodes), dim3(64), 0, stream,
+  hipLaunchKernelGGL(SelectBestKernel<64>, dim3(n_nodes), dim3(64), 0, stream,
                      gain, bins, dirs, lsum, n_features, out_best, k_dev);
-}
-
-extern "C" void gbt_evaluate(
-    const int64_t* hist, int n_nodes, int n_bins, int n_features,
-    const int32_t* cut_ptrs, const int64_t* parent_sums,
-    const float* maxabs, double g_scale,
-    double h_scale, double reg_lambda, double reg_alpha,
-    double max_delta_step, double min_child_weight, const int8_t* monotone,
-    const double* node_bounds, const uint8_t* feature_mask,
-    const uint8_t* cat_feature, double* out_gain, int32_t* out_bin,
-    uint8_t* out_dir, int64_t* out_lsum, const int32_t* k_dev,
-    int narrow_max, hipStream_t stream) {
-  gbt_evaluate_masked(hist, n_nodes, n_bins, n_features, cut_ptrs,
-                      parent_sums, maxabs, g_scale, h_scale, reg_lambda,
-                      reg_alpha, max_delta_step, min_child_weight, monotone,
-                      node_bounds, n_features, feature_mask, cat_feature,
-                      out_gain, out_bin, out_dir, out_lsum, k_dev,
-                      narrow_max, stream);
 }
 
 namespace {
@@ -706,12 +519,7 @@ void LaunchEvaluate(
     const int blocks =
         (int)std::min<long long>((total + 255) / 256, 16384);
     hipLaunchKernelGGL(EvaluateNarrowKernel, dim3(blocks), dim3(256), 0,
-                       stream, hist, n_nodes, n_bins, n_features, cut_ptrs,
-                       parent_sums, maxabs, k_dev, narrow_max, g_scale,
-                       h_scale, reg_lambda, reg_alpha, max_delta_step,
-                       min_child_weight, monotone, node_bounds, mask_stride,
-                       feature_mask,
-                       cat_feature, out_gain, out_bin, out_dir, out_lsum);
+                       stream, ea);
   }
 }
 

@@ -50,39 +50,26 @@ void gbt_partition(const uint8_t* gidx8, const uint16_t* gidx16,
                    int32_t* counters,              // [n_slots, 2] pre-init {seg_start, seg_end}
                    hipStream_t stream);
 
-void gbt_evaluate(const int64_t* hist /* [n_nodes, n_bins, 2] */,
-                  int n_nodes, int n_bins, int n_features,
-                  const int32_t* cut_ptrs, const int64_t* parent_sums,
-                  const float* maxabs,  // null, or [2] device max-abs:
-                                        // scales derived in-kernel
-                  double g_scale, double h_scale,
-                  double reg_lambda, double reg_alpha, double max_delta_step,
-                  double min_child_weight,
-                  const int8_t* monotone,        // [n_features] or null
-                  const double* node_bounds,     // [n_nodes, 2] or null
-                  const uint8_t* feature_mask,   // [n_nodes, n_features] or null
-                  const uint8_t* cat_feature,    // [n_features] or null
-                  double* out_gain,              // [n_nodes, n_features]
-                  int32_t* out_bin,              // [n_nodes, n_features]
-                  uint8_t* out_dir,              // [n_nodes, n_features]
-                  int64_t* out_lsum,             // [n_nodes, n_features, 2]
-                  const int32_t* k_dev,          // null, or live node count
-                  int narrow_max,  // >0: scalar kernel for narrow features
-                  hipStream_t stream);
-
-// mask_stride: n_features = per-node rows, 0 = one per-tree row
-void gbt_evaluate_masked(const int64_t* hist, int n_nodes, int n_bins,
-                         int n_features, const int32_t* cut_ptrs,
-                         const int64_t* parent_sums, const float* maxabs,
-                         double g_scale, double h_scale, double reg_lambda,
-                         double reg_alpha, double max_delta_step,
-                         double min_child_weight, const int8_t* monotone,
-                         const double* node_bounds, int mask_stride,
-                         const uint8_t* feature_mask,
-                         const uint8_t* cat_feature, double* out_gain,
-                         int32_t* out_bin, uint8_t* out_dir,
-                         int64_t* out_lsum, const int32_t* k_dev,
-                         int narrow_max, hipStream_t stream);
+void gbt_evaluate_masked(
+    const int64_t* hist /* [n_nodes, n_bins, 2] */, int n_nodes, int n_bins,
+    int n_features, const int32_t* cut_ptrs, const int64_t* parent_sums,
+    const float* maxabs,  // null, or [2] device max-abs: scales derived
+                          // in-kernel
+    double g_scale, double h_scale, double reg_lambda, double reg_alpha,
+    double max_delta_step, double min_child_weight,
+    const int8_t* monotone,       // [n_features] or null
+    const double* node_bounds,    // [n_nodes, 2] or null
+    int mask_stride,              // n_features = per-node mask rows,
+                                  // 0 = one per-tree row
+    const uint8_t* feature_mask,  // [n_nodes or 1, n_features] or null
+    const uint8_t* cat_feature,   // [n_features] or null
+    double* out_gain,             // [n_nodes, n_features]
+    int32_t* out_bin,             // [n_nodes, n_features]
+    uint8_t* out_dir,             // [n_nodes, n_features]
+    int64_t* out_lsum,            // [n_nodes, n_features, 2]
+    const int32_t* k_dev,         // null, or live node count
+    int narrow_max,  // >0: scalar kernel for narrow features
+    hipStream_t stream);
 
 // Same arguments and results as gbt_evaluate_masked, computed by the
 // single-wave reference kernel (one wave64 per (feature, node)).

@@ -7,33 +7,13 @@
 // One wave64 per (feature, node): loops targets, int64 scan per target,
 // accumulates summed gain per bin in registers (bins processed in
 // 64-wide chunks; per-chunk the lane owns one bin).  After the argmax,
-// a second pass re-derives the chosen bin's per-target left sums.
+// a second pass re-derives the chosen bin's per-target left sums.  The
+// per-target weight and gain are split_gain.h's; the validity rule, which
+// sums hessians across targets, is this kernel's own.
 #include "gbt_kernels.h"
+#include "split_gain.h"
 
 namespace {
-
-__device__ __forceinline__ double MtThresholdL1(double g, double alpha) {
-  if (alpha == 0.0) return g;
-  double s = (g > 0.0) ? 1.0 : ((g < 0.0) ? -1.0 : 0.0);
-  double m = fabs(g) - alpha;
-  return s * (m < 0.0 ? 0.0 : m);
-}
-
-struct MtParams {
-  double lam, alpha, mds, mcw;
-};
-
-__device__ __forceinline__ double MtWeight(double g, double h,
-                                           const MtParams& p) {
-  double w = -MtThresholdL1(g, p.alpha) / (h + p.lam);
-  if (p.mds > 0.0) w = fmin(fmax(w, -p.mds), p.mds);
-  return w;
-}
-
-__device__ __forceinline__ double MtGain(double g, double h, double w,
-                                         const MtParams& p) {
-  return -(2.0 * g * w + (h + p.lam) * (w * w));
-}
 
 // hists layout: [T, n_nodes, n_bins, 2]; parent sums [n_nodes, T, 2]
 __global__ __launch_bounds__(64) void MtEvaluateKernel(
@@ -47,7 +27,8 @@ __global__ __launch_bounds__(64) void MtEvaluateKernel(
     uint8_t* __restrict__ out_dir) {
   const int node = blockIdx.y;
   const int lane = threadIdx.x;
-  MtParams p{reg_lambda, reg_alpha, max_delta_step, min_child_weight};
+  const SplitParams p{reg_lambda, reg_alpha, max_delta_step,
+                      min_child_weight, -INFINITY, INFINITY};  // no bounds
   for (int f = blockIdx.x; f < n_features; f += gridDim.x) {
     const size_t out_idx = (size_t)node * n_features + f;
     if (feature_mask != nullptr && feature_mask[out_idx] == 0) {
@@ -70,7 +51,7 @@ __global__ __launch_bounds__(64) void MtEvaluateKernel(
       const double pg = parent_sums[((size_t)node * n_targets + t) * 2] * ig;
       const double ph =
           parent_sums[((size_t)node * n_targets + t) * 2 + 1] * ih;
-      parent_gain += MtGain(pg, ph, MtWeight(pg, ph, p), p);
+      parent_gain += GainGivenWeight(pg, ph, CalcWeight(pg, ph, p), p);
     }
 
     for (int dir = 0; dir < 2; ++dir) {
@@ -107,9 +88,10 @@ __global__ __launch_bounds__(64) void MtEvaluateKernel(
           const double ig = 1.0 / g_scales[t], ih = 1.0 / h_scales[t];
           const double gl = glq * ig, hl = hlq * ih;
           const double gr = grq * ig, hr = hrq * ih;
-          const double wl = MtWeight(gl, hl, p);
-          const double wr = MtWeight(gr, hr, p);
-          gain += MtGain(gl, hl, wl, p) + MtGain(gr, hr, wr, p);
+          const double wl = CalcWeight(gl, hl, p);
+          const double wr = CalcWeight(gr, hr, p);
+          gain += GainGivenWeight(gl, hl, wl, p) +
+                  GainGivenWeight(gr, hr, wr, p);
           hl_tot += hl;
           hr_tot += hr;
           hlq_tot += hlq;

@@ -84,6 +84,21 @@ class SplitEntry:
         return self.feature >= 0 and np.isfinite(self.gain) and self.gain > 0
 
 
+def feature_set_mask(feature_sets, k: int, n_features: int):
+    """Per-node sampled feature sets -> the [k, n_features] uint8 mask the
+    native evaluators take (a `None` set allows every feature), or None
+    when no node restricts its features."""
+    if feature_sets is None or all(fs is None for fs in feature_sets):
+        return None
+    mask = np.zeros((k, n_features), dtype=np.uint8)
+    for i, fs in enumerate(feature_sets):
+        if fs is None:
+            mask[i] = 1
+        else:
+            mask[i, np.asarray(fs, np.int64)] = 1
+    return mask
+
+
 def _sorted_cat_split(e: SplitEntry, node_hist: np.ndarray, pgq: int, phq: int,
                       f: int, cut_ptrs: np.ndarray, param: TrainParam,
                       inv_g: float, inv_h: float, parent_gain: float) -> None:
