@@ -1,7 +1,7 @@
 """Prediction throughput of the packed-node predictor (predict_bins.hip).
 
 One forest (100 trees, depth 8, 28 features; scalar leaves, plus a K=3
-vector-leaf variant) and three paths over the same rows:
+vector-leaf variant) and four paths over the same rows:
 
   (a) extmem   bst.predict(ExtMemQuantileDMatrix): pages uploaded and
                walked as stored (includes H2D of the pages, D2H of the
@@ -10,6 +10,13 @@ vector-leaf variant) and three paths over the same rows:
                (device events)
   (c) kernel_f the existing gbt_predict on the same rows as raw floats
                (device events; scalar leaves only)
+  (d) kernel_qf gbt_predict_q on those same device-resident float rows
+               (kind 0), timed in windows that alternate with (c) so that
+               the two see the same clocks; `qf_over_f` is the ratio of
+               the medians
+
+`--trees 1 --max-depth 6` is the per-round eval-set update, where reading
+the row dominates.
 
 Every path is warmed up, then timed `--repeats` times; the median, min
 and max rows/s are reported so the spread is visible.  One JSON line per
@@ -83,8 +90,21 @@ def _event_timed(fn, warmup, repeats, inner):
     return out
 
 
+def _event_timed_pair(fn_a, fn_b, warmup, repeats, inner):
+    """_event_timed for two calls whose windows alternate a, b, a, b."""
+    for _ in range(warmup):
+        fn_a()
+        fn_b()
+    out_a, out_b = [], []
+    for _ in range(repeats):
+        out_a += _event_timed(fn_a, 0, 1, inner)
+        out_b += _event_timed(fn_b, 0, 1, inner)
+    return out_a, out_b
+
+
 def run_variant(name, args, X, Xtrain, ytrain):
-    params = {"max_depth": 8, "max_bin": 256, "eta": 0.1, "device": "cuda",
+    params = {"max_depth": args.max_depth, "max_bin": 256, "eta": 0.1,
+              "device": "cuda",
               "objective": "reg:squarederror"}
     if name == "vector_k3":
         params["multi_strategy"] = "multi_output_tree"
@@ -92,7 +112,7 @@ def run_variant(name, args, X, Xtrain, ytrain):
     bst = xgb.train(params, dtrain, args.trees, verbose_eval=False)
     n = X.shape[0]
     res = {"variant": name, "rows": n, "features": X.shape[1],
-           "trees": len(bst.trees), "max_depth": 8,
+           "trees": len(bst.trees), "max_depth": args.max_depth,
            "nodes": int(sum(t.n_nodes for t in bst.trees)),
            "pages": args.pages}
     d_ext = ExtMemQuantileDMatrix(_Pages(np.array_split(X, args.pages)),
@@ -118,16 +138,26 @@ def run_variant(name, args, X, Xtrain, ytrain):
         args.warmup, args.repeats, args.inner))
     if name == "scalar":
         d_dev = xgb.DMatrix(torch.from_numpy(X).to(dev))
-        res["kernel_f_rows_per_s"] = _rates(n, _event_timed(
+        Xd = d_dev.device_data()
+        fa_f = _cached_forest_q(bst, 0, len(bst.trees), dev, None)
+        t_f, t_qf = _event_timed_pair(
             lambda: predict_margin_gpu(bst, d_dev, out, 0, len(bst.trees)),
-            args.warmup, args.repeats, args.inner))
-        # same rows, same forest: the two kernels must agree exactly when
-        # the split conditions are cut values
+            lambda: _launch_predict_q(fa_f, Xd, float("nan"), out, None),
+            args.warmup, args.repeats, args.inner)
+        res["kernel_f_rows_per_s"] = _rates(n, t_f)
+        res["kernel_qf_rows_per_s"] = _rates(n, t_qf)
+        res["qf_over_f"] = (res["kernel_qf_rows_per_s"]["median"]
+                            / res["kernel_f_rows_per_s"]["median"])
+        # same rows, same forest: the kernels must agree exactly (bins
+        # too, when the split conditions are cut values)
         a = torch.zeros((n, K), dtype=torch.float32, device=dev)
         b = torch.zeros((n, K), dtype=torch.float32, device=dev)
+        c = torch.zeros((n, K), dtype=torch.float32, device=dev)
         _launch_predict_q(fa, page, float("nan"), a, None)
         predict_margin_gpu(bst, d_dev, b, 0, len(bst.trees))
+        _launch_predict_q(fa_f, Xd, float("nan"), c, None)
         res["q_equals_f"] = bool(torch.equal(a, b))
+        res["qf_equals_f"] = bool(torch.equal(c, b))
     else:
         res["kernel_f_rows_per_s"] = None  # gbt_predict has no vector leaves
     return res
@@ -138,6 +168,7 @@ def main():
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--features", type=int, default=28)
     ap.add_argument("--trees", type=int, default=100)
+    ap.add_argument("--max-depth", type=int, default=8)
     ap.add_argument("--train-rows", type=int, default=100_000)
     ap.add_argument("--pages", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=2)

@@ -754,26 +754,6 @@ def test_gpu_lossguide_native_replay_matches_python_gpu_driver():
         assert abs(acc_g - acc_c) < 0.02, (params, acc_g, acc_c)
 
 
-def test_gpu_inplace_predict_device_resident():
-    """inplace_predict on a cuda tensor: zero-copy proxy straight into
-    the HIP predict kernel, forest SoA cached across calls."""
-    X, y = _data(20000, 8, seed=41)
-    d = xgb.DMatrix(X, label=y)
-    bst = xgb.train({"objective": "binary:logistic", "max_depth": 6,
-                     "device": "cuda"}, d, 10, verbose_eval=False)
-    ref = bst.predict(xgb.DMatrix(X))
-    Xd = torch.from_numpy(X).cuda()
-    got = bst.inplace_predict(Xd)
-    assert np.allclose(got, ref, atol=1e-6)
-    # repeated call reuses the cached device forest (same object)
-    fc = bst.__dict__.get("_forest_dev_cache", {})
-    assert len(fc) == 1
-    fa0 = next(iter(fc.values()))
-    got2 = bst.inplace_predict(Xd)
-    assert next(iter(fc.values())) is fa0
-    assert np.allclose(got2, ref, atol=1e-6)
-
-
 def test_gpu_mt_hist_fused_matches_per_target_loop():
     """Fused multi-target histogram (gbt_hist_mt, one pass over the bin
     matrix) must equal T single-target launches exactly (int64)."""

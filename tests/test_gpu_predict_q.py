@@ -2,7 +2,9 @@
 floats with vector leaves, leaf indices.  The oracle is always the CPU
 booster loaded from the same model JSON; margins and leaf ids are
 compared with exact equality (the kernel adds leaves in tree order with
-plain fp32 adds, like the host loops), DART weights excepted."""
+plain fp32 adds, like the host loops), DART weights excepted.  The
+tests at the end go through the public path for dense matrices with
+scalar leaves, whichever kernel serves it (today gbt_predict)."""
 import contextlib
 
 import numpy as np
@@ -362,3 +364,146 @@ def test_host_fallbacks_still_predict():
                                   categories=["blue", "red", "green"])
     d2 = xgb.DMatrix(df2, enable_categorical=True)
     assert np.allclose(bst.predict(d2), p_train, atol=1e-6)
+
+
+# -- dense matrices, scalar leaves: the public prediction path -------------
+
+def _scalar_model(n_out, missing):
+    """CPU-trained scalar-leaf forest (5 features, depth 4, 3 rounds) and
+    its rows; missing entries carry `missing` (NaN or a finite sentinel)."""
+    rng = np.random.RandomState(50 + n_out)
+    X = rng.randn(1000, 5).astype(np.float32)
+    X[rng.rand(1000, 5) < 0.15] = missing
+    Xz = np.where(X == missing, 0.0, np.nan_to_num(X))
+    params = {"max_depth": 4, "eta": 0.5, "max_bin": 32}
+    if n_out == 1:
+        y = (Xz[:, 0] * Xz[:, 1] + Xz[:, 2]).astype(np.float32)
+        params["objective"] = "reg:squarederror"
+    else:
+        y = np.argmax(Xz[:, :n_out] + 0.3 * rng.randn(1000, n_out)[:, :5],
+                      axis=1).astype(np.float32)
+        params.update(objective="multi:softprob", num_class=n_out)
+    bst = xgb.train(params, xgb.DMatrix(X, label=y, missing=missing), 3,
+                    verbose_eval=False)
+    assert bst.n_outputs == n_out and len(bst.trees) == 3 * n_out
+    assert all(t.leaf_values is None for t in bst.trees)
+    bm = rng.randn(1000, n_out).astype(np.float32)
+    return bst, X, bm
+
+
+@pytest.mark.parametrize("missing", [np.nan, -1.0])
+@pytest.mark.parametrize("n_out", [1, 3, 5])
+def test_dense_scalar_public_path(monkeypatch, n_out, missing):
+    """bst.predict / inplace_predict on a dense matrix with a scalar-leaf
+    forest equal the CPU booster exactly: 1, 3 and 5 output columns, NaN
+    and finite-sentinel missing values, a non-zero base_margin."""
+    trained, X, bm = _scalar_model(n_out, missing)
+    cpu, gpu = _reload(trained, "cpu"), _reload(trained, DEV)
+    if not np.isnan(missing):
+        assert (X == missing).any()
+    for n in (1, 257, 1000):
+        def dm():
+            return xgb.DMatrix(X[:n], missing=missing, base_margin=bm[:n])
+        for rng_ in ((0, 0), (1, 3)):
+            want = cpu.predict(dm(), output_margin=True,
+                               iteration_range=rng_)
+            with _device_only(monkeypatch):
+                got = gpu.predict(dm(), output_margin=True,
+                                  iteration_range=rng_)
+            assert got.shape == want.shape
+            assert np.array_equal(got, want), (n, rng_)
+        want = cpu.predict(dm(), output_margin=True)
+        want_plain = cpu.predict(xgb.DMatrix(X[:n], missing=missing),
+                                 output_margin=True)
+        assert not np.array_equal(want, want_plain)
+        Xd = torch.from_numpy(X[:n]).to(DEV)
+        with _device_only(monkeypatch):
+            got = gpu.inplace_predict(Xd, missing=missing,
+                                      predict_type="margin",
+                                      base_margin=bm[:n])
+            got_plain = gpu.inplace_predict(Xd, missing=missing,
+                                            predict_type="margin")
+        assert np.array_equal(got, want), n
+        assert np.array_equal(got_plain, want_plain), n
+
+
+def test_dense_categorical_public_path(monkeypatch):
+    """A set split that crosses the first 32-bit bitset word, walked on
+    raw floats through bst.predict."""
+    rng = np.random.RandomState(21)
+    n = 700
+    cat = rng.randint(0, 40, n).astype(np.float32)
+    Xn = rng.randn(n, 3).astype(np.float32)
+    X = np.concatenate([cat[:, None], Xn], axis=1)
+    X[rng.rand(n, 4) < 0.08] = np.nan
+    good = [1, 5, 7, 12, 19, 22, 28, 33, 36, 39]
+    y = (np.isin(cat, good) * 2.0 + 0.5 * np.nan_to_num(Xn[:, 0])
+         + 0.1 * rng.randn(n)).astype(np.float32)
+    ft = ["c", "q", "q", "q"]
+    trained = xgb.train({"max_depth": 4, "max_bin": 16,
+                         "max_cat_to_onehot": 1, "eta": 0.5},
+                        xgb.DMatrix(X, label=y, feature_types=ft), 4,
+                        verbose_eval=False)
+    assert any(len(c) > 1 and int(c.max()) >= 32 for t in trained.trees
+               for c in t.cat_segments.values())
+    cpu, gpu = _reload(trained, "cpu"), _reload(trained, DEV)
+    want = cpu.predict(xgb.DMatrix(X, feature_types=ft), output_margin=True)
+    want_leaf = cpu.predict(xgb.DMatrix(X, feature_types=ft), pred_leaf=True)
+    with _device_only(monkeypatch):
+        got = gpu.predict(xgb.DMatrix(X, feature_types=ft),
+                          output_margin=True)
+        got_leaf = gpu.predict(xgb.DMatrix(X, feature_types=ft),
+                               pred_leaf=True)
+    assert np.array_equal(got, want)
+    assert np.array_equal(got_leaf, want_leaf)
+
+
+def test_dart_drop_set_dense(monkeypatch):
+    """_predict_tree_subset and _predict_margin of a cuda DART booster on
+    a dense matrix against explicit per-tree fp32 adds of w * leaf."""
+    rng = np.random.RandomState(33)
+    X = rng.randn(700, 4).astype(np.float32)
+    X[rng.rand(700, 4) < 0.05] = np.nan
+    y = (np.nan_to_num(X[:, 0]) * 1.2 - np.nan_to_num(X[:, 1])
+         + 0.1 * rng.randn(700)).astype(np.float32)
+    trained = xgb.train({"booster": "dart", "max_depth": 3, "eta": 0.3,
+                         "rate_drop": 0.5, "seed": 3, "max_bin": 32},
+                        xgb.DMatrix(X, label=y), 8, verbose_eval=False)
+    gpu = _reload(trained, DEV)
+    assert len(gpu.weight_drop) == 8
+    idxs = [1, 2, 4, 7]
+    assert any(gpu.weight_drop[t] != 1.0 for t in idxs)
+    leaf = np.stack([t.predict_leaf_np(X) for t in gpu.trees], axis=1)
+
+    def oracle(start, trees):
+        out = np.full((700, 1), start, np.float32)
+        for t in trees:
+            tree = gpu.trees[t]
+            vals = tree.split_cond[:tree.n_nodes][leaf[:, t]]
+            out[:, gpu.tree_info[t]] += (vals.astype(np.float32)
+                                         * np.float32(gpu.weight_drop[t]))
+        return out
+
+    d = xgb.DMatrix(X)
+    with _device_only(monkeypatch):
+        got_sub = gpu._predict_tree_subset(d, idxs).cpu().numpy()
+        got_all = gpu._predict_margin(d).cpu().numpy()
+    assert np.array_equal(got_sub, oracle(0.0, idxs))
+    assert np.array_equal(got_all,
+                          oracle(gpu._base_margin_value(), range(8)))
+
+
+def test_vector_leaf_drop_set_dense(monkeypatch):
+    """The drop-set helper on a dense matrix with vector leaves walks on
+    the device like the margin does."""
+    X, Y = _vector_data(seed=9)
+    trained = xgb.train({"objective": "reg:squarederror", "max_depth": 4,
+                         "multi_strategy": "multi_output_tree", "eta": 0.3,
+                         "max_bin": 32}, xgb.DMatrix(X, label=Y), 5,
+                        verbose_eval=False)
+    cpu, gpu = _reload(trained, "cpu"), _reload(trained, DEV)
+    want = cpu._predict_tree_subset(xgb.DMatrix(X), [0, 2, 3]).numpy()
+    assert want.shape == (300, 3) and np.abs(want).max() > 0
+    with _device_only(monkeypatch):
+        got = gpu._predict_tree_subset(xgb.DMatrix(X), [0, 2, 3])
+    assert np.array_equal(got.cpu().numpy(), want)

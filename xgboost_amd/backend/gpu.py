@@ -780,6 +780,21 @@ class GpuOps(SegmentedOpsMixin):
 # prediction
 
 
+def _device_rows(dmat, device) -> torch.Tensor:
+    """The dense rows of `dmat` on `device`: its device-resident tensor
+    when it has one, otherwise an upload of the host rows."""
+    dd = dmat.device_data() if hasattr(dmat, "device_data") else None
+    if dd is not None:
+        return dd
+    return torch.from_numpy(dmat.raw_data()).to(device)
+
+
+def _missing_args(missing: float) -> Tuple[float, int]:
+    """(missing_value, missing_is_nan) as the kernels take them."""
+    is_nan = 1 if np.isnan(missing) else 0
+    return float(0.0 if is_nan else missing), is_nan
+
+
 class _ForestArrays:
     """Device SoA for a tree range [lo, hi) of a booster.  DART tree
     weights are folded into the LEAF values (margin = sum w_i*tree_i),
@@ -872,8 +887,7 @@ def shap_gpu(booster, dmat, lo: int, hi: int, phi: np.ndarray) -> np.ndarray:
             "GPU SHAP limits exceeded; falling back to CPU")
     device = booster.device
     fa = _ForestArrays(booster, lo, hi, device)
-    dd = dmat.device_data() if hasattr(dmat, 'device_data') else None
-    X = dd if dd is not None else torch.from_numpy(dmat.raw_data()).to(device)
+    X = _device_rows(dmat, device)
     expected = torch.tensor(
         [_expected_value(booster.trees[t]) for t in range(lo, hi)],
         dtype=torch.float64, device=device)
@@ -902,10 +916,8 @@ def _launch_shap_dfs(fa: _ForestArrays, X: torch.Tensor, n: int,
     the float32 out [n, n_groups, n_cols]."""
     from .. import ops as hip_ops
     lib = hip_ops.load()
-    missing_is_nan = 1 if np.isnan(missing) else 0
     lib.gbt_shap(
-        hip_ops.ptr(X), n, n_features,
-        float(0.0 if missing_is_nan else missing), missing_is_nan,
+        hip_ops.ptr(X), n, n_features, *_missing_args(missing),
         hip_ops.ptr(fa.tree_offsets), hip_ops.ptr(fa.left),
         hip_ops.ptr(fa.right), hip_ops.ptr(fa.split_index),
         hip_ops.ptr(fa.split_cond), hip_ops.ptr(fa.default_left),
@@ -955,11 +967,9 @@ def _launch_shap_paths(tab: _PathTable, Xt: torch.Tensor, n: int,
     float64 out [n_groups, n_cols, n]."""
     from .. import ops as hip_ops
     lib = hip_ops.load()
-    missing_is_nan = 1 if np.isnan(missing) else 0
     fn = lib.gbt_shap_paths if tab.max_elems <= 8 else lib.gbt_shap_paths16
-    fn(hip_ops.ptr(Xt), n, n_features,
-       float(0.0 if missing_is_nan else missing), missing_is_nan,
-       *tab.args(), n_groups, n_cols, hip_ops.ptr(out), hip_ops.stream())
+    fn(hip_ops.ptr(Xt), n, n_features, *_missing_args(missing), *tab.args(),
+       n_groups, n_cols, hip_ops.ptr(out), hip_ops.stream())
 
 
 def _launch_shap_ix(tab: _PathTable, Xt: torch.Tensor, n: int,
@@ -969,11 +979,9 @@ def _launch_shap_ix(tab: _PathTable, Xt: torch.Tensor, n: int,
     pair terms into the float64 out [n_groups, n_cols, n_cols, n]."""
     from .. import ops as hip_ops
     lib = hip_ops.load()
-    missing_is_nan = 1 if np.isnan(missing) else 0
     lib.gbt_shap_ix(
-        hip_ops.ptr(Xt), n, n_features,
-        float(0.0 if missing_is_nan else missing), missing_is_nan,
-        *tab.args(), n_groups, n_cols, hip_ops.ptr(out), hip_ops.stream())
+        hip_ops.ptr(Xt), n, n_features, *_missing_args(missing), *tab.args(),
+        n_groups, n_cols, hip_ops.ptr(out), hip_ops.stream())
 
 
 def _complete_diagonal(cube: torch.Tensor, base: torch.Tensor) -> torch.Tensor:
@@ -993,8 +1001,7 @@ def _shap_gpu_paths(booster, dmat, lo: int, hi: int,
     n, n_groups, n_cols = phi.shape
     device = booster.device
     tab = _PathTable(booster, lo, hi, device)
-    dd = dmat.device_data() if hasattr(dmat, "device_data") else None
-    X = dd if dd is not None else torch.from_numpy(dmat.raw_data()).to(device)
+    X = _device_rows(dmat, device)
     X = X.t().contiguous()  # [F, n]: coalesced per-feature gathers
     # phi transposed to [groups*cols, n] so the accumulation is coalesced
     out = torch.from_numpy(
@@ -1039,8 +1046,7 @@ def shap_interactions_gpu(booster, dmat, lo: int, hi: int,
     free, _total = torch.cuda.mem_get_info()
     if out_bytes > free - (2 << 30):
         raise ShapDeviceLimit("GPU SHAP interactions: output exceeds HBM")
-    dd = dmat.device_data() if hasattr(dmat, "device_data") else None
-    X = dd if dd is not None else torch.from_numpy(dmat.raw_data()).to(device)
+    X = _device_rows(dmat, device)
     X = X.t().contiguous()  # [F, n] coalesced gathers
     out = torch.zeros((n_groups, C, C, n), dtype=torch.float64,
                       device=device)
@@ -1236,14 +1242,10 @@ def predict_subset_gpu(booster, dmat, idxs, out: torch.Tensor
     device = out.device
     fa = _ForestArrays(booster, 0, 0, device, idxs=idxs,
                        fold_weights=True)
-    dd = dmat.device_data() if hasattr(dmat, "device_data") else None
-    X = dd if dd is not None else torch.from_numpy(dmat.raw_data()).to(device)
+    X = _device_rows(dmat, device)
     n = dmat.num_row()
-    missing = dmat.missing
-    missing_is_nan = 1 if np.isnan(missing) else 0
     lib.gbt_predict(
-        hip_ops.ptr(X), n, dmat.num_col(),
-        float(0.0 if missing_is_nan else missing), missing_is_nan,
+        hip_ops.ptr(X), n, dmat.num_col(), *_missing_args(dmat.missing),
         hip_ops.ptr(fa.tree_offsets), hip_ops.ptr(fa.left),
         hip_ops.ptr(fa.right), hip_ops.ptr(fa.split_index),
         hip_ops.ptr(fa.split_cond), hip_ops.ptr(fa.default_left),
@@ -1260,14 +1262,11 @@ def predict_margin_gpu(booster, dmat, out_margin: torch.Tensor,
     lib = hip_ops.load()
     device = out_margin.device
     fa = _cached_forest(booster, lo, hi, device)
-    dd = dmat.device_data() if hasattr(dmat, "device_data") else None
-    X = dd if dd is not None else torch.from_numpy(dmat.raw_data()).to(device)
+    X = _device_rows(dmat, device)
     n = dmat.num_row()
-    missing = dmat.missing
-    missing_is_nan = 1 if np.isnan(missing) else 0
     lib.gbt_predict(
-        hip_ops.ptr(X), n, dmat.num_col(), float(0.0 if missing_is_nan else missing),
-        missing_is_nan, hip_ops.ptr(fa.tree_offsets), hip_ops.ptr(fa.left),
+        hip_ops.ptr(X), n, dmat.num_col(), *_missing_args(dmat.missing),
+        hip_ops.ptr(fa.tree_offsets), hip_ops.ptr(fa.left),
         hip_ops.ptr(fa.right), hip_ops.ptr(fa.split_index),
         hip_ops.ptr(fa.split_cond), hip_ops.ptr(fa.default_left),
         hip_ops.ptr(fa.split_type), hip_ops.ptr(fa.cat_offsets),
@@ -1421,10 +1420,8 @@ def _launch_predict_q(fa: _ForestQ, X: torch.Tensor, missing: float,
     assert out_leaf is None or (out_leaf.is_contiguous()
                                 and out_leaf.dtype == torch.int32
                                 and out_leaf.shape == (n, fa.n_trees))
-    missing_is_nan = 1 if np.isnan(missing) else 0
     lib.gbt_predict_q(
-        hip_ops.ptr(X), kind, n, F,
-        float(0.0 if missing_is_nan else missing), missing_is_nan,
+        hip_ops.ptr(X), kind, n, F, *_missing_args(missing),
         hip_ops.ptr(fa.n_bins), hip_ops.ptr(fa.nodes),
         hip_ops.ptr(fa.tree_offsets), hip_ops.ptr(fa.cat_offsets),
         hip_ops.ptr(fa.cat_bits), hip_ops.ptr(fa.tree_group),
@@ -1433,15 +1430,37 @@ def _launch_predict_q(fa: _ForestQ, X: torch.Tensor, missing: float,
         hip_ops.stream())
 
 
-def predict_q_supported(dmat) -> bool:
-    """True when gbt_predict_q can read `dmat`: dense raw floats, or
-    external-memory pages stored as u8/u16 local bins."""
+def predict_forest_gpu(booster, dmat, lo: int, hi: int, idxs=None,
+                       out: Optional[torch.Tensor] = None,
+                       out_leaf: Optional[torch.Tensor] = None) -> bool:
+    """The device entry point of margins, DART drop sets and leaf ids: add
+    trees [lo, hi) (or the subset `idxs`) to `out` and/or write their leaf
+    ids to `out_leaf`.  Sparse CSR matrices go to gbt_predict_csr; margins
+    of scalar-leaf forests on dense raw floats to gbt_predict; vector
+    leaves, leaf ids and u8/u16 external-memory pages to gbt_predict_q.
+    Returns False, with nothing written, for what no kernel reads: pages
+    of int32 bins (the caller walks those on the host)."""
     from ..extmem import ExtMemQuantileDMatrix
+    if getattr(dmat, "_sparse_data", None) is not None:
+        predict_margin_csr_gpu(booster, dmat, out, lo, hi, idxs=idxs,
+                               out_leaf=out_leaf)
+        return True
     if isinstance(dmat, ExtMemQuantileDMatrix):
         # disk-spilled pages keep their dtype on the placeholder
-        return all(qm.gidx.dtype in (torch.uint8, torch.int16)
-                   for qm in dmat.pages)
-    return getattr(dmat, "_sparse_data", None) is None
+        if not all(qm.gidx.dtype in (torch.uint8, torch.int16)
+                   for qm in dmat.pages):
+            return False
+    elif out_leaf is None and not any(
+            booster.trees[t].leaf_values is not None
+            for t in (range(lo, hi) if idxs is None else idxs)):
+        if idxs is None:
+            predict_margin_gpu(booster, dmat, out, lo, hi)
+        else:
+            predict_subset_gpu(booster, dmat, idxs, out)
+        return True
+    predict_margin_q_gpu(booster, dmat, out, lo, hi, idxs=idxs,
+                         out_leaf=out_leaf)
+    return True
 
 
 def predict_margin_q_gpu(booster, dmat, out: Optional[torch.Tensor],
@@ -1462,9 +1481,7 @@ def predict_margin_q_gpu(booster, dmat, out: Optional[torch.Tensor],
     if fa.n_trees == 0:
         return out
     if not extmem:
-        dd = dmat.device_data() if hasattr(dmat, "device_data") else None
-        X = dd if dd is not None else \
-            torch.from_numpy(dmat.raw_data()).to(device)
+        X = _device_rows(dmat, device)
         _launch_predict_q(fa, X.contiguous(), dmat.missing, out, out_leaf)
         return out
     for pi in range(len(dmat.pages)):

@@ -345,59 +345,9 @@ class Booster:
                              idxs: List[int]) -> torch.Tensor:
         """sum(w_i * tree_i(X)) over the drop set, shaped like the
         margin cache."""
-        n = dmat.num_row()
-        out = torch.zeros((n, self.n_outputs), dtype=torch.float32,
-                          device=self.device)
-        if getattr(dmat, "_sparse_data", None) is not None:
-            if self.device.type == "cuda" and len(idxs) > 0:
-                from .backend.gpu import predict_margin_csr_gpu
-                return predict_margin_csr_gpu(self, dmat, out, 0, 0,
-                                              idxs=list(idxs))
-            return self._sparse_margin_add(dmat, out, list(idxs))
-        from .extmem import ExtMemQuantileDMatrix
-        if isinstance(dmat, ExtMemQuantileDMatrix):
-            # quantized-only pages: bin-based traversal per page (the
-            # split conds are cut values, so this is exact)
-            if self.device.type == "cuda":
-                from .backend.gpu import (predict_margin_q_gpu,
-                                          predict_q_supported)
-                if predict_q_supported(dmat):
-                    return predict_margin_q_gpu(self, dmat, out, 0, 0,
-                                                idxs=list(idxs))
-            # host walk: CPU boosters and int32-bin pages
-            for pi in range(len(dmat.pages)):
-                qm = dmat.page_qm(pi)
-                s, e = dmat.page_offsets[pi], dmat.page_offsets[pi + 1]
-                gg = qm.global_gidx().cpu().numpy()
-                for t in idxs:
-                    tree = self.trees[t]
-                    pos = tree.predict_leaf_bins(gg, dmat.cuts)
-                    if tree.leaf_values is not None:  # vector leaves
-                        out[s:e] += self._tw(t) * torch.as_tensor(
-                            tree.leaf_values[:tree.n_nodes][pos],
-                            device=out.device)
-                        continue
-                    vals = tree.split_cond[:tree.n_nodes][pos] * self._tw(t)
-                    out[s:e, self.tree_info[t]] += torch.as_tensor(
-                        vals, device=out.device)
-            return out
-        if self.device.type == "cuda" and not any(
-                self.trees[t].leaf_values is not None for t in idxs):
-            from .backend.gpu import predict_subset_gpu
-            return predict_subset_gpu(self, dmat, idxs, out)
-        X = dmat.raw_data()
-        for t in idxs:
-            tree = self.trees[t]
-            pos = tree.predict_leaf_np(X, dmat.missing)
-            if tree.leaf_values is not None:  # vector leaves
-                out += self._tw(t) * torch.as_tensor(
-                    tree.leaf_values[:tree.n_nodes][pos],
-                    device=out.device)
-            else:
-                vals = tree.split_cond[:tree.n_nodes][pos] * self._tw(t)
-                out[:, self.tree_info[t]] += torch.as_tensor(
-                    vals, device=out.device)
-        return out
+        out = torch.zeros((dmat.num_row(), self.n_outputs),
+                          dtype=torch.float32, device=self.device)
+        return self._add_trees(dmat, out, 0, 0, idxs=list(idxs))
 
     # -- training ------------------------------------------------------
     def update(self, dtrain: DMatrix, iteration: int,
@@ -954,52 +904,85 @@ class Booster:
                 out = out + self._linear.predict_margin(X)
             return out
         lo, hi = self._tree_range(iteration_range)
-        from .extmem import ExtMemQuantileDMatrix
-        if isinstance(dmat, ExtMemQuantileDMatrix):
-            return self._predict_margin_extmem(dmat, out, lo, hi)
-        if getattr(dmat, "_sparse_data", None) is not None:
-            if self.device.type == "cuda" and hi > lo:
-                from .backend.gpu import predict_margin_csr_gpu
-                return predict_margin_csr_gpu(self, dmat, out, lo, hi)
-            return self._predict_margin_sparse(dmat, out, lo, hi)
+        X = None
+        if self._recoded_frame(dmat):
+            # predict-frame categories re-coded to the training dictionary
+            # (reference encoder/ordinal.h Recode); the recoded matrix
+            # exists only on the host
+            from .data import align_categories
+            X = align_categories(dmat.raw_data(), dmat.categories_,
+                                 self.cat_categories_)
+        return self._add_trees(dmat, out, lo, hi, X=X)
+
+    def _recoded_frame(self, dmat) -> bool:
+        """True when `dmat` codes its categories differently from the
+        training frame."""
         train_cats = getattr(self, "cat_categories_", None)
         pred_cats = getattr(dmat, "categories_", None)
-        aligned = False
-        X = None
-        if train_cats and pred_cats and pred_cats != train_cats:
-            # predict-frame categories re-coded to the training dictionary
-            # (reference encoder/ordinal.h Recode)
-            from .data import align_categories
-            X = align_categories(dmat.raw_data(), pred_cats, train_cats)
-            aligned = True
-        has_mt = any(t.leaf_values is not None for t in self.trees[lo:hi])
-        if self.device.type == "cuda" and (hi - lo) > 0 and not aligned:
-            # device-resident inputs never round-trip to host here
-            if has_mt:  # vector leaves: packed-node kernel on raw floats
-                from .backend.gpu import predict_margin_q_gpu
-                return predict_margin_q_gpu(self, dmat, out, lo, hi)
-            from .backend.gpu import predict_margin_gpu
-            return predict_margin_gpu(self, dmat, out, lo, hi)
-        # host walk: CPU boosters and re-aligned categories (the recoded
-        # matrix exists only on the host)
-        if X is None:
-            X = dmat.raw_data()
-        for t in range(lo, hi):
+        return bool(train_cats and pred_cats and pred_cats != train_cats)
+
+    def _walk_on_device(self, dmat, lo: int, hi: int, idxs=None,
+                        out: Optional[torch.Tensor] = None,
+                        out_leaf: Optional[torch.Tensor] = None) -> bool:
+        """The device-or-host decision of every tree walk (margins, DART
+        drop sets, leaf ids).  Walks trees [lo, hi) or `idxs` on the GPU
+        and returns True, or returns False with nothing written: CPU
+        boosters, empty tree sets, re-coded categorical frames and what
+        the kernels cannot read (int32-bin pages) take the host walk."""
+        n_trees = hi - lo if idxs is None else len(idxs)
+        if self.device.type != "cuda" or n_trees <= 0 \
+                or self._recoded_frame(dmat):
+            return False
+        from .backend.gpu import predict_forest_gpu
+        return predict_forest_gpu(self, dmat, lo, hi, idxs=idxs, out=out,
+                                  out_leaf=out_leaf)
+
+    def _add_trees(self, dmat, out: torch.Tensor, lo: int, hi: int,
+                   idxs: Optional[List[int]] = None,
+                   X: Optional[np.ndarray] = None) -> torch.Tensor:
+        """out += sum(w_t * tree_t(row)) over trees [lo, hi) or `idxs`,
+        in tree order with fp32 adds on either side."""
+        if self._walk_on_device(dmat, lo, hi, idxs, out=out):
+            return out
+        trees = list(range(lo, hi)) if idxs is None else idxs
+        for t, rows, pos in self._host_leaf_ids(dmat, trees, X):
+            # the scalar-or-vector leaf accumulation of every host walk
             tree = self.trees[t]
-            pos = tree.predict_leaf_np(X, dmat.missing)
-            w = self._tw(t)
-            if tree.leaf_values is not None:
-                out += w * torch.as_tensor(
+            if tree.leaf_values is not None:  # vector leaves
+                out[rows] += self._tw(t) * torch.as_tensor(
                     tree.leaf_values[:tree.n_nodes][pos], device=out.device)
             else:
-                vals = tree.split_cond[:tree.n_nodes][pos]
-                out[:, self.tree_info[t]] += w * torch.as_tensor(
-                    vals, device=out.device)
+                out[rows, self.tree_info[t]] += self._tw(t) * torch.as_tensor(
+                    tree.split_cond[:tree.n_nodes][pos], device=out.device)
         return out
 
-    def _predict_margin_sparse(self, dmat, out: torch.Tensor,
-                               lo: int, hi: int) -> torch.Tensor:
-        return self._sparse_margin_add(dmat, out, list(range(lo, hi)))
+    def _host_leaf_ids(self, dmat, idxs: List[int],
+                       X: Optional[np.ndarray] = None):
+        """Host traversal of the trees `idxs`: yields (t, rows, leaf id of
+        each of those rows).  Sparse matrices walk their used columns,
+        external-memory matrices their quantized pages one by one (the
+        split conds are cut values, so bins are exact), dense ones the raw
+        rows (or the re-coded copy `X`)."""
+        from .extmem import ExtMemQuantileDMatrix
+        if not idxs:  # no trees: touch no rows and load no pages
+            return
+        if getattr(dmat, "_sparse_data", None) is not None:
+            for t, pos in self._sparse_leaf_ids(dmat, idxs):
+                yield t, slice(None), pos
+        elif isinstance(dmat, ExtMemQuantileDMatrix):
+            for pi in range(len(dmat.pages)):
+                # loads disk-spilled pages on demand
+                gg = dmat.page_qm(pi).global_gidx().cpu().numpy()
+                rows = slice(dmat.page_offsets[pi], dmat.page_offsets[pi + 1])
+                for t in idxs:
+                    yield t, rows, self.trees[t].predict_leaf_bins(
+                        gg, dmat.cuts)
+        else:
+            if X is None:
+                X = dmat.raw_data()
+            for t in idxs:
+                yield t, slice(None), self.trees[t].predict_leaf_np(
+                    X, dmat.missing)
 
     def _sparse_leaf_ids(self, dmat, idxs: List[int]):
         """Host sparse traversal: yields (t, leaf id per row) for the
@@ -1034,88 +1017,16 @@ class Booster:
                 tree.split_index[:tree.n_nodes] = saved
             yield t, pos
 
-    def _sparse_margin_add(self, dmat, out: torch.Tensor,
-                           idxs: List[int]) -> torch.Tensor:
-        """Host sparse predict: add the trees `idxs` to `out`."""
-        for t, pos in self._sparse_leaf_ids(dmat, idxs):
-            tree = self.trees[t]
-            w = self._tw(t)
-            if tree.leaf_values is not None:  # vector leaves
-                out += w * torch.as_tensor(
-                    tree.leaf_values[:tree.n_nodes][pos], device=out.device)
-            else:
-                vals = tree.split_cond[:tree.n_nodes][pos]
-                out[:, self.tree_info[t]] += w * torch.as_tensor(
-                    vals, device=out.device)
-        return out
-
-    def _predict_margin_extmem(self, dmat, out: torch.Tensor,
-                               lo: int, hi: int) -> torch.Tensor:
-        """Bin-based traversal per quantized page (no raw values)."""
-        if self.device.type == "cuda":
-            from .backend.gpu import (predict_margin_q_gpu,
-                                      predict_q_supported)
-            if predict_q_supported(dmat):
-                return predict_margin_q_gpu(self, dmat, out, lo, hi)
-        # host walk: CPU boosters and int32-bin pages (> 65535 local bins)
-        for pi in range(len(dmat.pages)):
-            qm = dmat.page_qm(pi)  # loads disk-spilled pages on demand
-            s, e = dmat.page_offsets[pi], dmat.page_offsets[pi + 1]
-            gg = qm.global_gidx().cpu().numpy()
-            for t in range(lo, hi):
-                tree = self.trees[t]
-                pos = tree.predict_leaf_bins(gg, dmat.cuts)
-                if tree.leaf_values is not None:  # vector leaves
-                    out[s:e] += self._tw(t) * torch.as_tensor(
-                        tree.leaf_values[:tree.n_nodes][pos],
-                        device=out.device)
-                    continue
-                vals = tree.split_cond[:tree.n_nodes][pos]
-                out[s:e, self.tree_info[t]] += self._tw(t) * torch.as_tensor(
-                    vals, device=out.device)
-        return out
-
     def _predict_leaf(self, data: DMatrix, lo: int, hi: int) -> np.ndarray:
         """Leaf node id of every row in trees [lo, hi): int32 [n, hi-lo]."""
-        from .extmem import ExtMemQuantileDMatrix
-        extmem = isinstance(data, ExtMemQuantileDMatrix)
-        sparse = getattr(data, "_sparse_data", None) is not None
-        if sparse and self.device.type == "cuda" and hi > lo:
-            from .backend.gpu import predict_margin_csr_gpu
-            leaf = torch.empty((data.num_row(), hi - lo),
-                               dtype=torch.int32, device=self.device)
-            predict_margin_csr_gpu(self, data, None, lo, hi, out_leaf=leaf)
+        shape = (data.num_row(), max(hi - lo, 0))
+        leaf = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if self._walk_on_device(data, lo, hi, out_leaf=leaf):
             return leaf.cpu().numpy()
-        if sparse:  # host walk on the used columns
-            ids = [pos for _, pos in
-                   self._sparse_leaf_ids(data, list(range(lo, hi)))]
-            if not ids:
-                return np.zeros((data.num_row(), 0), np.int32)
-            return np.stack(ids, axis=1)
-        if self.device.type == "cuda" and hi > lo:
-            from .backend.gpu import predict_margin_q_gpu, predict_q_supported
-            train_cats = getattr(self, "cat_categories_", None)
-            pred_cats = getattr(data, "categories_", None)
-            aligned = bool(train_cats and pred_cats
-                           and pred_cats != train_cats)
-            if predict_q_supported(data) and not aligned:
-                leaf = torch.empty((data.num_row(), hi - lo),
-                                   dtype=torch.int32, device=self.device)
-                predict_margin_q_gpu(self, data, None, lo, hi, out_leaf=leaf)
-                return leaf.cpu().numpy()
-        # host walk: CPU boosters, re-aligned categorical frames and
-        # int32-bin pages
-        if extmem:
-            pages = []
-            for pi in range(len(data.pages)):
-                gg = data.page_qm(pi).global_gidx().cpu().numpy()
-                pages.append(np.stack(
-                    [self.trees[t].predict_leaf_bins(gg, data.cuts)
-                     for t in range(lo, hi)], axis=1))
-            return np.concatenate(pages, axis=0)
-        X = data.raw_data()
-        return np.stack([self.trees[t].predict_leaf_np(X, data.missing)
-                         for t in range(lo, hi)], axis=1)
+        ids = np.zeros(shape, np.int32)
+        for t, rows, pos in self._host_leaf_ids(data, list(range(lo, hi))):
+            ids[rows, t - lo] = pos
+        return ids
 
     def _tree_range(self, iteration_range: Tuple[int, int]) -> Tuple[int, int]:
         lo_it, hi_it = iteration_range
