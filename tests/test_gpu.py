@@ -254,7 +254,15 @@ def test_gpu_e2e_quality():
     assert res["train"]["auc"][-1] > 0.9
 
 
-def test_gpu_shap_matches_cpu():
+def _shap_device_only(monkeypatch):
+    """The host SHAP recursion raises while the block runs, so a silent
+    fallback from the device fails the test."""
+    import shap_cases
+    from xgboost_amd import shap
+    return shap_cases.host_recursion_raises(monkeypatch, shap)
+
+
+def test_gpu_shap_matches_cpu(monkeypatch):
     from xgboost_amd.shap import shap_values
     X, y = _data(500, 8)
     d = xgb.DMatrix(X, label=y)
@@ -263,7 +271,8 @@ def test_gpu_shap_matches_cpu():
     cpu_contribs = bst.predict(d, pred_contribs=True)
     bst.set_param("device", "cuda")
     bst.reset()
-    gpu_contribs = bst.predict(d, pred_contribs=True)
+    with _shap_device_only(monkeypatch):
+        gpu_contribs = bst.predict(d, pred_contribs=True)
     assert gpu_contribs.shape == cpu_contribs.shape
     assert np.allclose(cpu_contribs, gpu_contribs, atol=1e-4), \
         np.abs(cpu_contribs - gpu_contribs).max()
@@ -272,13 +281,14 @@ def test_gpu_shap_matches_cpu():
     assert np.allclose(gpu_contribs.sum(axis=1), margin, atol=1e-3)
 
 
-def test_gpu_shap_with_missing():
+def test_gpu_shap_with_missing(monkeypatch):
     from xgboost_amd.shap import shap_values
     X, y = _data(300, 6, missing_frac=0.2)
     d = xgb.DMatrix(X, label=y)
     bst = xgb.train({"objective": "binary:logistic", "max_depth": 4,
                      "device": "cuda"}, d, 4, verbose_eval=False)
-    contribs = bst.predict(d, pred_contribs=True)
+    with _shap_device_only(monkeypatch):
+        contribs = bst.predict(d, pred_contribs=True)
     margin = bst.predict(d, output_margin=True)
     assert np.allclose(contribs.sum(axis=1), margin, atol=1e-3)
 
@@ -591,7 +601,7 @@ def test_gpu_approx_matches_cpu():
                               tg.split_index[:tg.n_nodes])
 
 
-def test_gpu_shap_multiclass_matches_cpu():
+def test_gpu_shap_multiclass_matches_cpu(monkeypatch):
     """Path-table SHAP with n_groups > 1: per-group bias and the
     transposed phi indexing must match the CPU oracle."""
     rng = np.random.RandomState(17)
@@ -604,7 +614,8 @@ def test_gpu_shap_multiclass_matches_cpu():
     ref = bc.predict(dc, pred_contribs=True)
     dg = xgb.DMatrix(X, label=y)
     bg = xgb.train({**params, "device": "cuda"}, dg, 4)
-    got = bg.predict(dg, pred_contribs=True)
+    with _shap_device_only(monkeypatch):
+        got = bg.predict(dg, pred_contribs=True)
     assert got.shape == ref.shape == (3000, 3, 7)
     np.testing.assert_allclose(got, ref, atol=5e-4, rtol=1e-3)
 
@@ -653,7 +664,7 @@ def test_gpu_lambdarank_device_gradients():
     assert float(res2.split(":")[-1]) > 0.8, res2
 
 
-def test_gpu_shap_interactions_matches_cpu():
+def test_gpu_shap_interactions_matches_cpu(monkeypatch):
     """pred_interactions on GPU (shap_ix.hip) vs the exact CPU
     conditional TreeSHAP."""
     from xgboost_amd.shap import shap_interactions
@@ -669,7 +680,8 @@ def test_gpu_shap_interactions_matches_cpu():
     # same data/params -> identical trees (tested elsewhere); compare
     # the GPU interactions of the GPU model vs CPU interactions of it
     bst_g.device = bst_g.device  # noqa: B018
-    got = shap_interactions(bst_g, dg)
+    with _shap_device_only(monkeypatch):
+        got = shap_interactions(bst_g, dg)
     cpu_of_g = None
     import torch as _t
     dev = bst_g.device

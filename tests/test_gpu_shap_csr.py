@@ -14,6 +14,7 @@ import pytest
 import scipy.sparse as sp
 import torch
 
+import shap_cases as sc
 import xgboost_amd as xgb
 from xgboost_amd.tree_model import RegTree
 from test_shap_csr import (_categorical_forest, _comb, _dense_nan,
@@ -24,10 +25,6 @@ from test_shap_csr import (_categorical_forest, _comb, _dense_nan,
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-
-
-def _boom(*a, **k):
-    raise AssertionError("host SHAP recursion used on the device path")
 
 
 @contextlib.contextmanager
@@ -43,9 +40,7 @@ def _device_only(monkeypatch, chunk_rows=None):
         chunks.append((row_begin, tile.shape[1]))
         return gather(csr_dev, row_begin, col_map, tile)
 
-    with monkeypatch.context() as m:
-        m.setattr(shap, "_tree_shap", _boom)
-        m.setattr(shap, "_saabas", _boom)
+    with sc.host_recursion_raises(monkeypatch, shap) as m:
         m.setattr(gpu_backend, "_gather_csr_columns", counted)
         m.setattr(gpu_backend, "_SHAP_CSR_CHUNK_ROWS", chunk_rows)
         yield chunks

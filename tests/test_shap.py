@@ -86,10 +86,12 @@ def test_path_pair_decomposition_matches_exact_interactions():
     """Python mirror of the shap_ix.hip algorithm (extend once, unwind
     each element b, accumulate conditional pair terms) vs the exact
     conditioned-TreeSHAP CPU implementation — validates the math the
-    GPU kernel runs."""
+    GPU kernel runs — and both against the Shapley interaction index
+    computed from its definition (shap_cases.shapley_interactions)."""
+    import shap_cases as sc
     import xgboost_amd as xgb
     from xgboost_amd.shap import shap_interactions, shap_values
-    from xgboost_amd.shap_paths import build_path_table
+    from xgboost_amd.shap_paths import build_path_table, element_agrees
 
     def extend_pw(zs, ones):
         pw = [1.0]
@@ -155,15 +157,12 @@ def test_path_pair_decomposition_matches_exact_interactions():
         for i in range(n):
             ones = []
             for j in range(M):
-                x = X[i, fs[j]]
-                if np.isnan(x):
-                    ok = bool(emiss[s + j])
-                else:
-                    ok = elo[s + j] <= x < ehi[s + j]
+                ok = element_agrees(X[i, fs[j]], elo[s + j], ehi[s + j],
+                                    emiss[s + j])
                 ones.append(1.0 if ok else 0.0)
             pw = extend_pw(zs, ones)
             for b in range(M):
-                mult = 0.5 * v * (ones[b] - zs[b])
+                mult = 0.25 * v * (ones[b] - zs[b])
                 if mult == 0.0:
                     continue
                 pwb = unwind_pw(pw, zs[b], ones[b], M)
@@ -178,6 +177,16 @@ def test_path_pair_decomposition_matches_exact_interactions():
         out[:, i_, i_] = base[:, i_] - (out[:, i_, :].sum(axis=-1)
                                         - out[:, i_, i_])
     assert np.allclose(out, ref, atol=1e-4), np.abs(out - ref).max()
+    want = sc.with_base(
+        sc.shapley_interactions(bst.trees, bst.tree_info, X), bst)[:, 0]
+    # `out` is fp64 but for its diagonal, completed from the float32
+    # contributions: 2^-23 S (k + 1) there, and for `ref`, cast once
+    sc.assert_close(out.astype(np.float32), want, bst.trees, cube=True,
+                    what="mirror")
+    sc.assert_close(ref.astype(np.float32), want, bst.trees, cube=True,
+                    what="host")
+    off = ~np.eye(C, dtype=bool)
+    assert np.abs(out[:, off] - want[:, off]).max() <= 1e-12 * sc.scale(want)
 
 
 def test_contribs_strict_shape():

@@ -1025,10 +1025,11 @@ def shap_interactions_gpu(booster, dmat, lo: int, hi: int,
     src/predictor/interpretability/shap.cu:1068).
 
     Per (row, path): extend once, unwind each element b, and accumulate
-    0.5*v*(one_b-z_b)*(one_a-z_a)*UnwoundSum_a over the reduced path —
-    the exact conditional-TreeSHAP pair terms (validated against the
-    CPU implementation by tests/test_shap.py).  Diagonal/bias cells are
-    completed from the contribution vector like the CPU path."""
+    0.25*v*(one_b-z_b)*(one_a-z_a)*UnwoundSum_a over the reduced path
+    into both cells of the pair — the Shapley interaction index
+    (checked against its definition by tests/test_gpu_shap_exact.py).
+    Diagonal/bias cells are completed from the contribution vector like
+    the CPU path."""
     from .. import ops as hip_ops
     from ..shap import shap_values
     lib = hip_ops.load()

@@ -173,10 +173,19 @@ __global__ __launch_bounds__(128) void ShapKernel(
           UnwindPath(path, len, idx);
         }
         if (fr.depth + 1 <= kMaxDepth) {
-          stack[sp++] = Frame{cold, fr.depth + 1, len, f,
-                              (float)(iz * cold_zero), 0.0f};
-          stack[sp++] = Frame{hot, fr.depth + 1, len, f,
-                              (float)(iz * hot_zero), (float)io};
+          // an element with zero == one == 0 (a child without cover that
+          // the row does not enter) zeroes every weight below it, and
+          // UnwoundSum would divide by it: prune the branch, like the
+          // host recursion
+          const float cz = (float)(iz * cold_zero);
+          const float hz = (float)(iz * hot_zero);
+          const float ho = (float)io;
+          if (cz != 0.0f) {
+            stack[sp++] = Frame{cold, fr.depth + 1, len, f, cz, 0.0f};
+          }
+          if (hz != 0.0f || ho != 0.0f) {
+            stack[sp++] = Frame{hot, fr.depth + 1, len, f, hz, ho};
+          }
         }
       }
     }

@@ -8,18 +8,21 @@
 // (pweights pw), then for every element b UNWIND b from pw — giving
 // the pweights of the path conditioned on feature b — and accumulate,
 // for every other element a,
-//   w = 0.5 * v * (one_b - z_b) * (one_a - z_a) * UnwoundSum_a(pw \ b)
-// into out[f_a][f_b] AND out[f_b][f_a]; summed over both conditioning
-// directions this reproduces the CPU implementation's
-// `out[:, j, :] += diff; out[:, :, j] += diff` exactly (validated by
-// tests/test_shap.py::test_path_pair_decomposition...).  O(M^3) fp64
-// per (row, path) with M <= 16 path elements.
+//   w = 0.25 * v * (one_b - z_b) * (one_a - z_a) * UnwoundSum_a(pw \ b)
+// into out[f_a][f_b] AND out[f_b][f_a].  The conditional difference
+// (on - off) / 2 for the ordered pair (a, b) is the Shapley interaction
+// index Phi_ab; each cell receives it once from either order, hence the
+// further 1/2, and the cube is exactly symmetric (checked against the
+// subset-sum definition by tests/test_gpu_shap_exact.py and, in a numpy
+// mirror, by tests/test_shap.py::test_path_pair_decomposition...).
+// O(M^3) fp64 per (row, path) with M <= 16 path elements.
 //
 // Output is [group][C][C][row] (rows innermost) so each thread owns
 // its row slice: coalesced accumulation, no atomics.  Diagonal and
 // bias cells are completed on the host from the contribution vector:
 // out[i][i] = phi_i - sum_{j != i} out[i][j].
 #include "gbt_kernels.h"
+#include "shap_interval.h"
 
 namespace {
 
@@ -50,10 +53,9 @@ __global__ __launch_bounds__(256) void ShapIxKernel(
         const int f = ef[s + j];
         fs[j] = f;
         const float x = X[(size_t)f * n_rows + row];
-        const bool miss =
-            missing_is_nan ? isnan(x) : (isnan(x) || x == missing_value);
-        const bool ok = miss ? (emiss[s + j] != 0)
-                             : (x >= elo[s + j] && x < ehi[s + j]);
+        const bool ok = ShapElementAgrees(x, elo[s + j], ehi[s + j],
+                                          emiss[s + j] != 0, missing_value,
+                                          missing_is_nan);
         ones[j] = ok ? 1.0 : 0.0;
         zs[j] = ez[s + j];
         rzs[j] = erz[s + j];
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(256) void ShapIxKernel(
       double* og = out + (size_t)grp * C * C * n_rows + row;
       const int d = M;
       for (int b = 0; b < M; ++b) {
-        const double mult = 0.5 * v * (ones[b] - zs[b]);
+        const double mult = 0.25 * v * (ones[b] - zs[b]);
         if (mult == 0.0) continue;
         // unwind b: pweights of the path without b (depth d-1)
         double pwb[kD];

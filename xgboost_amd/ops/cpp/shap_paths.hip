@@ -12,6 +12,7 @@
 // scratch-bandwidth-bound at ~100k rows/s; this formulation is
 // fp64-rate-bound.
 #include "gbt_kernels.h"
+#include "shap_interval.h"
 
 namespace {
 
@@ -65,10 +66,9 @@ __global__ __launch_bounds__(256) void ShapPathsKernel(
         if (j < M) {
           const int f = ef[s + j];
           const float x = X[(size_t)f * n_rows + row];
-          const bool miss =
-              missing_is_nan ? isnan(x) : (isnan(x) || x == missing_value);
-          const bool ok = miss ? (emiss[s + j] != 0)
-                               : (x >= elo[s + j] && x < ehi[s + j]);
+          const bool ok = ShapElementAgrees(x, elo[s + j], ehi[s + j],
+                                            emiss[s + j] != 0, missing_value,
+                                            missing_is_nan);
           ones[j] = ok ? 1.0 : 0.0;
           zs[j] = ez[s + j];
           rzs[j] = erz[s + j];

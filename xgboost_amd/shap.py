@@ -14,6 +14,18 @@ last column the bias (expected value incl. base_score); interactions
 A sparse CSR DMatrix is explained in the compact space of the columns
 the forest splits on (absent entries and stored NaNs are missing) and
 expanded to full width at the end, on the CPU and on the GPU alike.
+
+Off-diagonal interaction cells hold the Shapley interaction index
+Phi_ij (half the pair's joint effect in each of [i, j] and [j, i]); the
+diagonal is phi_i minus the rest of its row.  A child without cover has
+weight 0.
+
+Output dtype: every route returns float32 (computed in fp64 and cast
+once; the DFS kernel accumulates in float32), except dense device
+pred_contribs on a numeric forest, which returns the path kernel's
+float64 as it is.  Only an ImportError (kernels not built, or a
+ShapDeviceLimit) sends a device call to the host recursion; any other
+exception from the device code is a bug and propagates.
 """
 from __future__ import annotations
 
@@ -97,7 +109,9 @@ def _tree_shap(tree: RegTree, x: np.ndarray, phi: np.ndarray,
 
     def recurse(nid: int, path: List[List[float]], zero: float, one: float,
                 pfeat: int, cond_frac: float) -> None:
-        if cond_frac == 0.0:
+        # an element with zero == one == 0 (a cold child without cover)
+        # zeroes every weight below it: prune, nothing divides by it
+        if cond_frac == 0.0 or (zero == 0.0 and one == 0.0):
             return
         path = [list(e) for e in path]
         if condition == 0 or condition_feature != pfeat:
@@ -174,8 +188,8 @@ def shap_values(booster, dmat, iteration_range=(0, 0),
         try:
             from .backend.gpu import shap_gpu
             return shap_gpu(booster, dmat, lo, hi, phi)
-        except (ImportError, AttributeError):
-            pass
+        except ImportError:
+            pass  # kernels not built, or a ShapDeviceLimit: exact host
     _host_contribs(booster.trees[lo:hi], booster.tree_info[lo:hi], X, phi,
                    dmat.missing, approx)
     if n_groups == 1:
@@ -216,7 +230,7 @@ def shap_interactions(booster, dmat, iteration_range=(0, 0)) -> np.ndarray:
             from .backend.gpu import shap_interactions_gpu
             return shap_interactions_gpu(booster, dmat, lo, hi,
                                          iteration_range)
-        except (ImportError, AttributeError):
+        except ImportError:
             pass  # categorical / deep-path forests: exact CPU fallback
     X = dmat.raw_data()
     n_groups = booster.n_outputs
@@ -248,7 +262,9 @@ def _host_interactions(trees, groups, X: np.ndarray, base: np.ndarray,
                            condition=1, condition_feature=j)
                 _tree_shap(tree, X[i], phi_off[i], missing,
                            condition=-1, condition_feature=j)
-            diff = (phi_on - phi_off) / 2.0
+            # (on - off) / 2 is the index of the ordered pair (i, j); it
+            # goes into both cells, so each gets half from either order
+            diff = (phi_on - phi_off) / 4.0
             diff[:, j] = 0.0
             out[:, k, j, :] += diff
             out[:, k, :, j] += diff

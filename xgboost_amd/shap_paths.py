@@ -66,6 +66,17 @@ def _unwound_sum(zeros: List[float], ones: List[float], idx: int) -> float:
     return total
 
 
+def element_agrees(x, lo, hi, miss_ok, missing: float = np.nan):
+    """Whether a row's value x follows a path element, as the kernels
+    test it (ops/cpp/shap_interval.h): a missing value by the element's
+    flag, any other by lo <= x < hi.  An upper end of +inf is unbounded,
+    so that +inf agrees with it as it goes right in the tree walk."""
+    x = np.float32(x)
+    if np.isnan(x) or (not np.isnan(missing) and x == np.float32(missing)):
+        return bool(miss_ok)
+    return bool(x >= lo and (x < hi or hi == np.inf))
+
+
 def build_path_table(trees, tree_groups) -> Tuple[np.ndarray, ...]:
     """Flatten a numeric forest into the per-path element table.
 
