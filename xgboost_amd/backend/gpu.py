@@ -1566,3 +1566,119 @@ def predict_margin_csr_gpu(booster, dmat, out: Optional[torch.Tensor],
     _launch_predict_csr(fa, indptr, indices, values, dmat.num_col(), out,
                         out_leaf, 1 if force_search else 0, grid_cap)
     return out
+
+
+# ---------------------------------------------------------------------------
+# LambdaMART gradients (lambdarank.hip)
+
+LAMBDARANK_MAX_GROUP = 2048  # kMaxGroup: the largest tier's LDS capacity
+LAMBDARANK_METRICS = {"ndcg": 0, "map": 1, "pairwise": 2}
+# tier name -> (largest group, kernel tier id).  The kernel has two block
+# shapes for "mid" (ids 1/2: 128/256 threads) and for "large" (ids 3/4:
+# 256/512 threads); the ids here are the ones measured faster: 128 and
+# 512 threads (profiles/lambdarank_mi355x.md).
+LAMBDARANK_TIERS = {"wave": (64, 0), "mid": (256, 1), "large": (2048, 4)}
+
+
+def lambdarank_schedule(group_ptr: np.ndarray) -> dict:
+    """Work lists for the ranking kernel, plain numpy: every non-empty
+    group's id in the list of the smallest tier that holds it, largest
+    groups first within a tier (the long blocks start first; ties keep
+    group order).  `eligible` is False when a group exceeds
+    LAMBDARANK_MAX_GROUP or the pointer does not cover [0, N) in order."""
+    gp = np.asarray(group_ptr, np.int64).reshape(-1)
+    cnt = np.diff(gp)
+    max_group = int(cnt.max()) if cnt.size else 0
+    ok = bool(gp.size >= 1 and gp[0] == 0 and (cnt >= 0).all()
+              and max_group <= LAMBDARANK_MAX_GROUP)
+    lists = {}
+    lo = 0
+    for name, (cap, _) in LAMBDARANK_TIERS.items():
+        ids = np.nonzero((cnt > lo) & (cnt <= cap))[0]
+        ids = ids[np.argsort(-cnt[ids], kind="stable")]
+        lists[name] = ids.astype(np.int32)
+        lo = cap
+    return {"lists": lists, "max_group": max_group, "eligible": ok}
+
+
+def lambdarank_doc_weight(weights, group_ptr: np.ndarray):
+    """Per-document fp64 weight: instance weights as they are, group
+    weights spread over their documents with G / sum(w) folded in
+    (reference ranking_utils.cc:44).  None without weights."""
+    if weights is None:
+        return None
+    w = np.asarray(weights, np.float64).reshape(-1)
+    gp = np.asarray(group_ptr, np.int64).reshape(-1)
+    G = gp.size - 1
+    if w.shape[0] == G:
+        return np.repeat(w, np.diff(gp)) * (G / max(float(w.sum()), 1e-300))
+    return w
+
+
+class LambdaRankState:
+    """What the ranking kernel needs besides the scores, built once per
+    (MetaInfo, device): device labels and group pointer, the work list of
+    every tier, the per-document weight, 1/IDCG per group (rank:ndcg; it
+    depends on the labels only) and whether the labels are binary
+    (rank:map checks this once here, not every round)."""
+
+    def __init__(self, labels, group_ptr, weights, device,
+                 inv_idcg: Optional[np.ndarray] = None):
+        y = np.ascontiguousarray(np.asarray(labels).reshape(-1), np.float32)
+        gp = np.ascontiguousarray(np.asarray(group_ptr).reshape(-1),
+                                  np.int64)
+        sched = lambdarank_schedule(gp)
+        self.n = int(y.shape[0])
+        self.n_groups = int(gp.size - 1)
+        self.max_group = sched["max_group"]
+        self.eligible = bool(sched["eligible"] and int(gp[-1]) == self.n)
+        self.binary_labels = bool(((y == 0) | (y == 1)).all())
+        if not self.eligible:
+            return
+        self.labels = torch.from_numpy(y).to(device)
+        self.group_ptr = torch.from_numpy(gp).to(device)
+        self.work = {name: torch.from_numpy(ids).to(device)
+                     for name, ids in sched["lists"].items() if ids.size}
+        w = lambdarank_doc_weight(weights, gp)
+        self.weight = (None if w is None else
+                       torch.from_numpy(np.ascontiguousarray(w)).to(device))
+        self.inv_idcg = (None if inv_idcg is None else torch.from_numpy(
+            np.ascontiguousarray(inv_idcg, np.float64)).to(device))
+
+
+def lambdarank_gpair_gpu(scores: torch.Tensor, state: LambdaRankState,
+                         metric: str, k: int, score_norm: bool,
+                         normalize: bool, exp_gain: bool
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """LambdaMART (g, h), fp32 [N], for fp32 device scores [N]: one kernel
+    launch per non-empty tier, top-k pair method.  The kernel writes every
+    document, so the outputs are not cleared first."""
+    from .. import ops as hip_ops
+    lib = hip_ops.load()
+    if not hasattr(lib, "gbt_lambdarank"):
+        raise RuntimeError("libgbt_hip.so has no gbt_lambdarank; rebuild it "
+                           "(xgboost_amd/ops/build_ext.py --force)")
+    if not state.eligible:
+        raise ValueError(
+            f"ranking kernel: groups of up to {LAMBDARANK_MAX_GROUP} "
+            f"documents covering every row, got {state.max_group}")
+    m = LAMBDARANK_METRICS[metric]
+    if metric == "map" and not state.binary_labels:
+        raise ValueError("rank:map requires binary labels")
+    if metric == "ndcg" and state.inv_idcg is None:
+        raise ValueError("rank:ndcg needs the state's inv_idcg")
+    assert (scores.is_cuda and scores.dtype == torch.float32
+            and scores.is_contiguous() and scores.numel() == state.n)
+    g = torch.empty(state.n, dtype=torch.float32, device=scores.device)
+    h = torch.empty_like(g)
+    for name, work in state.work.items():
+        cap, tier = LAMBDARANK_TIERS[name]
+        assert lib.gbt_lambdarank_tier_cap(tier) == cap, (name, tier)
+        lib.gbt_lambdarank(
+            m, tier, hip_ops.ptr(scores), hip_ops.ptr(state.labels),
+            hip_ops.ptr(state.group_ptr), hip_ops.ptr(state.inv_idcg),
+            hip_ops.ptr(state.weight), hip_ops.ptr(work), work.numel(),
+            int(k), int(bool(score_norm)), int(bool(normalize)),
+            int(bool(exp_gain)), hip_ops.ptr(g), hip_ops.ptr(h),
+            hip_ops.stream())
+    return g, h

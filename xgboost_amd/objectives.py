@@ -17,6 +17,8 @@ loops.  Each objective provides:
 from __future__ import annotations
 
 import math
+import os
+import weakref
 from typing import Callable, Dict, Optional, Tuple
 
 import numpy as np
@@ -633,7 +635,8 @@ def _pbool(v, default: bool) -> bool:
 
 class _LambdaRankBase(Objective):
     """LambdaMART gradients, fully vectorized torch ops (device-resident
-    when predictions live on the GPU).
+    when predictions live on the GPU); the top-k pair method on the GPU
+    runs as a HIP kernel instead, see get_gradient.
 
     Reference math reproduced exactly (src/objective/lambdarank_obj.h):
     - LambdaGrad (:93): sigma = sigmoid(s_high - s_low),
@@ -775,8 +778,69 @@ class _LambdaRankBase(Objective):
     def _delta_vec(self, stats, y_high, y_low, rank_high, rank_low, g):
         raise NotImplementedError
 
+    # -- HIP kernel path ---------------------------------------------------
+    _hip_metric: Optional[str] = None  # kernel metric name (subclasses)
+
+    def _hip_state(self, preds, info):
+        """The ranking kernel's per-dataset state when this call can run
+        on it, else None (see get_gradient).  Built once per (MetaInfo,
+        device) and held through a weak reference to the MetaInfo; a
+        replaced label, group or weight array rebuilds it."""
+        if not (preds.is_cuda and preds.dtype == torch.float32
+                and self._hip_metric is not None
+                and self.pair_method == "topk" and not self.unbiased
+                and os.environ.get("XGB_AMD_RANK_HIP", "1") != "0"):
+            return None
+        from . import ops as hip_ops
+        if not hasattr(hip_ops.load(), "gbt_lambdarank"):
+            return None
+        ent = self.__dict__.get("_hip_cache")
+        key = (info.labels, info.group_ptr, info.weights)
+        if (ent is None or ent[0]() is not info or ent[1] != preds.device
+                or any(a is not b for a, b in zip(ent[2], key))):
+            from .backend.gpu import LambdaRankState
+            gp_np = self._groups(info)
+            inv_idcg = None
+            if self._hip_metric == "ndcg":
+                # IDCG sorts by label, so the document order serves as the
+                # "ranked" list it is handed
+                gp = torch.as_tensor(gp_np)
+                cnt = gp[1:] - gp[:-1]
+                gid = torch.repeat_interleave(torch.arange(cnt.numel()), cnt)
+                y = torch.as_tensor(
+                    np.asarray(info.labels, np.float64).reshape(-1))
+                pos = torch.arange(y.numel()) - gp[gid]
+                inv_idcg = self._prepare(y, cnt, gp, pos)["inv_idcg"].numpy()
+            state = LambdaRankState(info.labels, gp_np, info.weights,
+                                    preds.device, inv_idcg)
+            self_ref = weakref.ref(self)
+
+            def _evict(_, self_ref=self_ref):
+                obj = self_ref()
+                if obj is not None:
+                    obj.__dict__.pop("_hip_cache", None)
+
+            ent = (weakref.ref(info, _evict), preds.device, key, state)
+            self._hip_cache = ent
+        return ent[3] if ent[3].eligible else None
+
     # -- main --------------------------------------------------------------
     def get_gradient(self, preds, info, it):
+        """Device predictions with the top-k pair method run as one HIP
+        kernel launch per group-size tier (ops/cpp/lambdarank.hip).  The
+        torch formulation below serves everything else: CPU tensors, the
+        `mean` pair method (host RNG), unbiased LambdaMART (position state
+        across groups and rounds), a group above the kernel's capacity
+        (backend.gpu.LAMBDARANK_MAX_GROUP documents), a library without
+        the kernel, and XGB_AMD_RANK_HIP=0."""
+        state = self._hip_state(preds, info)
+        if state is not None:
+            from .backend.gpu import lambdarank_gpair_gpu
+            g, h = lambdarank_gpair_gpu(
+                preds.detach().contiguous().view(-1), state,
+                self._hip_metric, self._k(), self.score_norm, self.normalize,
+                self.exp_gain)
+            return g.view(preds.shape), h.view(preds.shape)
         dev = preds.device
         p = preds.detach().double().reshape(-1)
         N = p.numel()
@@ -972,6 +1036,8 @@ class _LambdaRankBase(Objective):
 
 @register("rank:ndcg")
 class LambdaRankNDCG(_LambdaRankBase):
+    _hip_metric = "ndcg"
+
     @property
     def default_metric(self):
         return "ndcg"
@@ -1011,6 +1077,8 @@ class LambdaRankNDCG(_LambdaRankBase):
 
 @register("rank:map")
 class LambdaRankMAP(_LambdaRankBase):
+    _hip_metric = "map"
+
     @property
     def default_metric(self):
         return "map"
@@ -1063,6 +1131,8 @@ class LambdaRankMAP(_LambdaRankBase):
 
 @register("rank:pairwise")
 class LambdaRankPairwise(_LambdaRankBase):
+    _hip_metric = "pairwise"
+
     @property
     def default_metric(self):
         return "map"

@@ -57,6 +57,11 @@ _SIGS = {
     "gbt_gpair_fused": [_i, _p, _p, _p, _f, _i64, _p, _p, _p],
     "gbt_quantize": [_p, _i64, _d, _d, _p, _p, _p, _p],
     "gbt_margin_add": [_p, _p, _p, _i64, _i, _i, _p],
+    # metric, tier, scores, labels, group_ptr, inv_idcg, weight, work,
+    # n_work, k, score_norm, normalize, exp_gain, out_g, out_h
+    "gbt_lambdarank": [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i,
+                       _p, _p, _p],
+    "gbt_lambdarank_tier_cap": [_i],
     "gbt_hist_cpu": [_p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i],
     "gbt_partition_cpu": [_p, _p, _i, _p, _i64, _i64, _i, _i, _i, _p, _i,
                           _i, _p],
@@ -136,6 +141,8 @@ def load() -> ctypes.CDLL:
         _lib.gbt_root_tasks_check.restype = _c.c_int
     if hasattr(_lib, "gbt_wt_arena_bytes"):
         _lib.gbt_wt_arena_bytes.restype = _c.c_longlong
+    if hasattr(_lib, "gbt_lambdarank_tier_cap"):
+        _lib.gbt_lambdarank_tier_cap.restype = _c.c_int
     if hasattr(_lib, "gbt_partition_cpu"):
         _lib.gbt_partition_cpu.restype = _c.c_longlong
     return _lib

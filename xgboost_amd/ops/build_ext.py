@@ -4,6 +4,7 @@ import glob
 import os
 import subprocess
 import sys
+import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "cpp")
@@ -13,7 +14,17 @@ SOURCES = ["hist.hip", "partition.hip", "evaluate.hip", "compress.hip",
            "predict.hip", "predict_bins.hip", "predict_csr.hip", "shap.hip",
            "shap_paths.hip", "shap_ix.hip", "shap_csr.hip",
            "driver.hip", "csr.hip", "gpair.hip", "mt_evaluate.hip",
-           "cpu_hist.cpp"]
+           "cpu_hist.cpp", "lambdarank.hip"]
+
+# Sources compiled on their own, with flags the other kernels were not
+# measured under: lambdarank.hip keeps the compiler from pairing fp32
+# operations into packed instructions and prints the per-kernel resource
+# usage (registers, LDS, scratch, occupancy; profiles/lambdarank_mi355x.md).
+OWN_FLAGS = {
+    "lambdarank.hip": ["-Xclang", "-target-feature", "-Xclang",
+                       "-packed-fp32-ops",
+                       "-Rpass-analysis=kernel-resource-usage"],
+}
 
 
 def build(force: bool = False) -> str:
@@ -25,12 +36,27 @@ def build(force: bool = False) -> str:
         if os.path.getmtime(OUT) >= newest:
             return OUT
     hipcc = os.environ.get("HIPCC", "hipcc")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17",
-           "-ffp-contract=off",  # bit-match the numpy fp64 oracle
-           "-fopenmp",           # native CPU hist/partition (cpu_hist.cpp)
-           "-shared", "-fPIC", "-o", OUT] + sources
-    print("+", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
+    common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17",
+              "-ffp-contract=off",  # bit-match the numpy fp64 oracle
+              "-fopenmp",           # native CPU hist/partition (cpu_hist.cpp)
+              "-fPIC"]
+    with tempfile.TemporaryDirectory() as tmp:
+        inputs = []
+        for src in sources:
+            own = OWN_FLAGS.get(os.path.basename(src))
+            if own is None:
+                inputs.append(src)
+                continue
+            obj = os.path.join(tmp, os.path.basename(src) + ".o")
+            cmd = common + own + ["-c", src, "-o", obj]
+            print("+", " ".join(cmd), flush=True)
+            subprocess.check_call(cmd)
+            # ahead of the sources: hipcc's "-x hip" in front of a .hip
+            # file holds for every file after it, objects included
+            inputs.insert(0, obj)
+        cmd = common + ["-shared", "-o", OUT] + inputs
+        print("+", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
     return OUT
 
 

@@ -165,6 +165,23 @@ void gbt_copy_ranges(const int32_t* src, int32_t* dst,
                      const BlockTask* tasks, int n_tasks,
                      hipStream_t stream);
 
+// LambdaMART gradients for the groups in `work` (lambdarank.hip), one
+// launch per tier.  metric: 0 = ndcg, 1 = map, 2 = pairwise.  tier picks
+// the group capacity and block shape; every group in `work` has between 1
+// and gbt_lambdarank_tier_cap(tier) documents.  Writes g and h of every
+// document of those groups (final fp32 values; no pre-zeroing needed).
+void gbt_lambdarank(int metric, int tier, const float* scores,
+                    const float* labels,
+                    const long long* group_ptr,  // [G+1]
+                    const double* inv_idcg,      // [G], ndcg only
+                    const double* weight,        // [N] per document, or null
+                    const int32_t* work, int n_work, int k, int score_norm,
+                    int normalize, int exp_gain, float* out_g, float* out_h,
+                    hipStream_t stream);
+
+// Largest group a tier holds; 0 for an unknown tier.
+int gbt_lambdarank_tier_cap(int tier);
+
 void gbt_select_best(const double* gain, const int32_t* bins,
                      const uint8_t* dirs, const int64_t* lsum, int n_nodes,
                      int n_features, int64_t* out_best,
