@@ -7,7 +7,14 @@ measurement (median / min / max in ms) and one per output comparison.
 Shape (a): 1M documents in 10k groups of 100, feature_bench.py's labels,
 scores from a few boosting rounds.  Shape (b): about 1M documents in
 seeded log-normal group sizes clipped to 1..1251, same scores.
---tiers also times the kernel's alternative block shapes."""
+--tiers also times the kernel's alternative block shapes.
+
+--metrics times the ranking metrics instead (rank_metric.hip): Booster.
+eval_set per call at shape (a) for ndcg, map@10 and pre@10, the kernel
+against XGB_AMD_RANK_METRIC_HIP=0; the kernel's block shapes at shape (b)
+and at shape (c), 61 groups of 16384; and one group of 2^m documents on
+the kernel against the host's copy + argsort, which sets
+RANK_METRIC_MAX_GROUP."""
 import argparse
 import json
 import os
@@ -95,6 +102,97 @@ def tiers(name, shape, info, preds, calls, warmup):
                           "max_ms": round(float(np.max(t)), 4)}), flush=True)
 
 
+def _report(bench, extra, t, calls):
+    t = np.asarray(t)
+    print(json.dumps(dict({"bench": bench}, **extra, calls=calls,
+                          median_ms=round(float(np.median(t)), 4),
+                          min_ms=round(float(t.min()), 4),
+                          max_ms=round(float(t.max()), 4))), flush=True)
+
+
+def _timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def metrics_ab(bst, shape, d, calls, warmup):
+    """Booster.eval_set per call (margin cached), the ranking-metric kernel
+    (XGB_AMD_RANK_METRIC_HIP=1) against the host loop (=0), alternated."""
+    for metric in ("ndcg", "map@10", "pre@10"):
+        bst.set_param("eval_metric", metric)
+        times, outs = {"1": [], "0": []}, {}
+        for i in range(warmup + calls):
+            for flag in ("1", "0"):
+                os.environ["XGB_AMD_RANK_METRIC_HIP"] = flag
+                ms, outs[flag] = _timed(lambda: bst.eval_set([(d, "e")]))
+                if i >= warmup:
+                    times[flag].append(ms)
+        os.environ.pop("XGB_AMD_RANK_METRIC_HIP")
+        for flag, path in (("1", "hip"), ("0", "host")):
+            _report(f"eval_set {metric} {shape}",
+                    {"path": path, "value": outs[flag].split(":")[-1]},
+                    times[flag], calls)
+
+
+def _metric_kernel_times(variants, info, scores, kinds, calls, warmup):
+    """rank_metric_gpu alone per (block shape, metric), alternated."""
+    states = {v: gpu_backend.RankMetricState(
+        info.labels, info.group_ptr, scores.device, block)
+        for v, block in variants.items()}
+    times = {(v, k): [] for v in variants for k in kinds}
+    for i in range(warmup + calls):
+        for v, state in states.items():
+            for k in kinds:
+                ms, _ = _timed(lambda: gpu_backend.rank_metric_gpu(
+                    scores, state, k, 10, False))
+                if i >= warmup:
+                    times[(v, k)].append(ms)
+    return times
+
+
+METRIC_SHAPES = {"256x8 tile 1024": (2048, 1), "256x4 tile 1024": (1024, 2),
+                 "512x4 tile 1024": (2048, 3), "256x8 tile 256": (2048, 4)}
+
+
+def metric_shapes(shape, info, scores, calls, warmup):
+    """The metric kernel with each alternative block shape."""
+    times = _metric_kernel_times(METRIC_SHAPES, info, scores,
+                                 ("ndcg", "map"), calls, warmup)
+    for (v, k), t in times.items():
+        _report(f"rank_metric_gpu {k}@10 {shape}", {"block": v}, t, calls)
+
+
+def metric_cap(calls, warmup, lo=12, hi=21):
+    """One group of 2^m documents: the kernel against the host path for the
+    same group (device-to-host copy + stable argsort), per metric."""
+    rng = np.random.RandomState(5)
+    saved = gpu_backend.RANK_METRIC_MAX_GROUP
+    gpu_backend.RANK_METRIC_MAX_GROUP = 1 << hi
+    try:
+        for m in range(lo, hi + 1):
+            n = 1 << m
+            info = _info(rng.randint(0, 2, n).astype(np.float32), [n])
+            scores = torch.from_numpy(rng.randn(n).astype(np.float32)).cuda()
+            c = max(3, calls // (1 + max(0, m - 15) * 4))
+            times = _metric_kernel_times(
+                {"256x8 tile 1024": (2048, 1), "256x4 tile 1024": (1024, 2)},
+                info, scores, ("ndcg", "map"), c, warmup)
+            for (v, k), t in times.items():
+                _report(f"one group 2^{m} {k}@10", {"path": "hip " + v}, t, c)
+            host = []
+            for i in range(warmup + c):
+                ms, _ = _timed(lambda: np.argsort(
+                    -scores.cpu().numpy().astype(np.float64), kind="stable"))
+                if i >= warmup:
+                    host.append(ms)
+            _report(f"one group 2^{m}", {"path": "host copy+argsort"}, host, c)
+    finally:
+        gpu_backend.RANK_METRIC_MAX_GROUP = saved
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000)
@@ -102,6 +200,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--tiers", action="store_true")
+    ap.add_argument("--metrics", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark measures the GPU"
 
@@ -125,6 +224,16 @@ def main():
               "b": (_info(y[:nb], sizes_b), preds[:nb].contiguous())}
     ybin = (y >= 2).astype(np.float32)
 
+    if args.metrics:
+        metrics_ab(bst, "a", d, args.calls, args.warmup)
+        nc = 61 * 16384
+        shapes["c"] = (_info(y[:nc], np.full(61, 16384)),
+                       preds[:nc].contiguous())
+        for shape in ("b", "c"):
+            info, p = shapes[shape]
+            metric_shapes(shape, info, p.view(-1), args.calls, args.warmup)
+        metric_cap(args.calls, args.warmup)
+        return
     for name in ("rank:ndcg", "rank:map", "rank:pairwise"):
         info = _info(ybin, sizes_a) if name == "rank:map" else shapes["a"][0]
         ab(name, "a", info, preds, args.calls, args.warmup)

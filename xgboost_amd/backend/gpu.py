@@ -9,6 +9,7 @@ whole-tree mode runs with ONE host sync per tree.
 """
 from __future__ import annotations
 
+import weakref
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -1682,3 +1683,174 @@ def lambdarank_gpair_gpu(scores: torch.Tensor, state: LambdaRankState,
             int(bool(exp_gain)), hip_ops.ptr(g), hip_ops.ptr(h),
             hip_ops.stream())
     return g, h
+
+
+# ---------------------------------------------------------------------------
+# Ranking metrics ndcg / map / pre by counting (rank_metric.hip)
+
+RANK_METRIC_KINDS = {"ndcg": 0, "map": 1, "pre": 2}
+# tier name -> (documents per work item, kernel tier id).  The kernel has
+# four block shapes (ids 1..4); id 2, 256 threads x 4 documents with a
+# 1024-key tile, is the one measured fastest at ordinary group sizes
+# (profiles/lambdarank_mi355x.md).
+RANK_METRIC_TIERS = {"wave": (64, 0), "block": (1024, 2)}
+RANK_METRIC_SLAB = RANK_METRIC_TIERS["block"][0]
+# The work is quadratic in the group size: 2^18 is the largest power of
+# two at which one group on the kernel still beats the host's copy +
+# argsort of it for every metric (13.4 against 17.2 ms for map; 44 against
+# 37 ms at 2^19, profiles/lambdarank_mi355x.md).  A call with a larger
+# group takes the host path whole.
+RANK_METRIC_MAX_GROUP = 1 << 18
+
+
+def rank_metric_schedule(group_ptr: np.ndarray,
+                         slab: int = RANK_METRIC_SLAB) -> dict:
+    """Work lists for the ranking-metric kernel, plain numpy.  `wave`: ids
+    of the groups of 1..64 documents, in group order.  `block`: one
+    (group, slab start) row per `slab` documents of every larger group,
+    largest groups first (each item streams its whole group, so these are
+    the long blocks; ties keep group order), a group's slabs in order.
+    `part_off[g]` is group g's first slot in the partial buffer, one slot
+    per work item; empty groups have none.  `eligible` is False when a
+    group exceeds RANK_METRIC_MAX_GROUP or the pointer is not an ordered
+    cover starting at 0."""
+    gp = np.asarray(group_ptr, np.int64).reshape(-1)
+    cnt = np.diff(gp)
+    wave_cap = RANK_METRIC_TIERS["wave"][0]
+    max_group = int(cnt.max()) if cnt.size else 0
+    ok = bool(gp.size >= 1 and gp[0] == 0 and (cnt >= 0).all()
+              and max_group <= RANK_METRIC_MAX_GROUP)
+    big = cnt > wave_cap
+    n_items = np.where(big, -(-cnt // slab), (cnt > 0).astype(np.int64))
+    part_off = np.concatenate([[0], np.cumsum(n_items)])
+    ids = np.nonzero(big)[0]
+    ids = ids[np.argsort(-cnt[ids], kind="stable")]
+    reps = n_items[ids]
+    first = np.cumsum(reps) - reps  # index of each group's first item
+    item_group = np.repeat(ids, reps)
+    item_start = (np.arange(int(reps.sum())) - np.repeat(first, reps)) * slab
+    return {"wave": np.nonzero((cnt > 0) & ~big)[0].astype(np.int32),
+            "block": np.stack([item_group, item_start], 1).astype(np.int32),
+            "part_off": part_off.astype(np.int32), "max_group": max_group,
+            "eligible": ok and int(part_off[-1]) < 2 ** 31}
+
+
+class RankMetricState:
+    """What the ranking-metric kernel needs besides the scores, built once
+    per (MetaInfo, device): device labels and group pointer, the work
+    lists, 1/n_relevant per group (map) and a per-k cache of 1/IDCG
+    (ndcg; it depends on the labels and k only).  A normaliser of 0 marks
+    a group that takes the metric's default value.  `block` overrides the
+    block tier's (slab, kernel tier id), for timing the other shapes."""
+
+    def __init__(self, labels, group_ptr, device,
+                 block: Tuple[int, int] = RANK_METRIC_TIERS["block"]):
+        y = np.ascontiguousarray(np.asarray(labels).reshape(-1), np.float32)
+        gp = np.ascontiguousarray(np.asarray(group_ptr).reshape(-1),
+                                  np.int64)
+        self.tiers = dict(RANK_METRIC_TIERS, block=block)
+        sched = rank_metric_schedule(gp, block[0])
+        self.n = int(y.shape[0])
+        self.n_groups = int(gp.size - 1)
+        self.counts = np.diff(gp)
+        self.max_group = sched["max_group"]
+        self.eligible = bool(sched["eligible"] and int(gp[-1]) == self.n)
+        if not self.eligible:
+            return
+        self.labels = torch.from_numpy(y).to(device)
+        self.group_ptr = torch.from_numpy(gp).to(device)
+        self.work = {name: torch.from_numpy(sched[name]).to(device)
+                     for name in RANK_METRIC_TIERS if sched[name].size}
+        self.part_off = torch.from_numpy(sched["part_off"]).to(device)
+        self.n_partial = int(sched["part_off"][-1])
+        gid = np.repeat(np.arange(self.n_groups), self.counts)
+        n_rel = np.bincount(gid, weights=y > 0, minlength=self.n_groups)
+        with np.errstate(divide="ignore"):
+            inv = np.where(n_rel > 0, 1.0 / n_rel, 0.0)
+        self.inv_n_relevant = torch.from_numpy(inv).to(device)
+        # metrics.ndcg gives a group whose labels sum to 0 the default
+        lsum = np.bincount(gid, weights=y.astype(np.float64),
+                           minlength=self.n_groups)
+        self._label_sum_zero = torch.from_numpy(lsum == 0).to(device)
+        self._inv_idcg = {}
+
+    def inv_idcg(self, topn: int) -> torch.Tensor:
+        """1/IDCG@topn per group: the ndcg kernel with the labels as the
+        scores (equal labels have equal gains, so their order is free)."""
+        inv = self._inv_idcg.get(topn)
+        if inv is None:
+            idcg = _rank_metric_launch(self.labels, self, "ndcg", topn,
+                                       None, 0.0)
+            inv = torch.where((idcg > 0) & ~self._label_sum_zero,
+                              1.0 / idcg, torch.zeros_like(idcg))
+            self._inv_idcg[topn] = inv
+        return inv
+
+
+def _rank_metric_launch(scores, state, kind, topn, scale, dflt):
+    from .. import ops as hip_ops
+    lib = hip_ops.load()
+    partial = torch.empty(state.n_partial, dtype=torch.float64,
+                          device=scores.device)
+    out = torch.empty(state.n_groups, dtype=torch.float64,
+                      device=scores.device)
+    for name, work in state.work.items():
+        slab, tier = state.tiers[name]
+        assert lib.gbt_rank_metric_slab(tier) == slab, (name, tier)
+        lib.gbt_rank_metric(
+            RANK_METRIC_KINDS[kind], tier, hip_ops.ptr(scores),
+            hip_ops.ptr(state.labels), hip_ops.ptr(state.group_ptr),
+            hip_ops.ptr(work), work.shape[0], int(topn),
+            hip_ops.ptr(state.part_off), hip_ops.ptr(partial),
+            hip_ops.stream())
+    lib.gbt_rank_metric_finish(
+        hip_ops.ptr(partial), hip_ops.ptr(state.part_off),
+        hip_ops.ptr(scale), float(dflt), hip_ops.ptr(out), state.n_groups,
+        hip_ops.stream())
+    return out
+
+
+def rank_metric_gpu(scores: torch.Tensor, state: RankMetricState, kind: str,
+                    topn: int, minus: bool = False) -> torch.Tensor:
+    """Per-group ndcg@topn or map@topn values, or for `pre` the per-group
+    number of relevant documents in the top min(topn, n), as fp64 [G] on
+    the device of the fp32 scores [N].  Groups without a relevant document
+    (empty ones included) take 0 with `minus`, else 1.  No host sync."""
+    from .. import ops as hip_ops
+    if not hasattr(hip_ops.load(), "gbt_rank_metric"):
+        raise RuntimeError("libgbt_hip.so has no gbt_rank_metric; rebuild it "
+                           "(xgboost_amd/ops/build_ext.py --force)")
+    if not state.eligible:
+        raise ValueError(
+            f"ranking-metric kernel: groups of up to {RANK_METRIC_MAX_GROUP} "
+            f"documents covering every row, got {state.max_group}")
+    assert (scores.is_cuda and scores.dtype == torch.float32
+            and scores.is_contiguous() and scores.numel() == state.n)
+    topn = max(0, min(int(topn), 2 ** 31 - 1))
+    scale = {"ndcg": lambda: state.inv_idcg(topn),
+             "map": lambda: state.inv_n_relevant, "pre": lambda: None}[kind]()
+    return _rank_metric_launch(scores, state, kind, topn, scale,
+                               0.0 if minus else 1.0)
+
+
+_RANK_METRIC_STATES: dict = {}
+
+
+def rank_metric_state(info, device) -> RankMetricState:
+    """The RankMetricState of (info, device), held through a weak
+    reference to the MetaInfo and rebuilt when its label or group array is
+    replaced.  Without a group pointer every row is one group."""
+    slot = (id(info), str(device))
+    key = (info.labels, info.group_ptr)
+    ent = _RANK_METRIC_STATES.get(slot)
+    if (ent is None or ent[0]() is not info
+            or any(a is not b for a, b in zip(ent[1], key))):
+        n = int(np.asarray(info.labels).reshape(-1).shape[0])
+        gp = (np.array([0, n], np.int64) if info.group_ptr is None
+              else info.group_ptr)
+        state = RankMetricState(info.labels, gp, device)
+        ref = weakref.ref(
+            info, lambda _, slot=slot: _RANK_METRIC_STATES.pop(slot, None))
+        ent = (ref, key, state)
+        _RANK_METRIC_STATES[slot] = ent
+    return ent[2]

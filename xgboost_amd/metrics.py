@@ -10,10 +10,18 @@ Metrics are evaluated on *transformed* predictions except where the
 reference evaluates on margins (logloss uses probabilities; we receive
 whatever Booster.eval passes, which mirrors the reference: objective
 pred_transform applied first except for output_margin-style metrics).
+
+Device-resident metrics (`_torch_ok`) reduce on the predictions' device
+and sync one scalar pair: rmse, mae, logloss, error, merror, mlogloss,
+binary auc, and the ranking metrics ndcg, map and pre, which run the
+counting kernel ops/cpp/rank_metric.hip for fp32 HIP predictions (see
+_rank_metric_device for what stays on the numpy path).
 """
 from __future__ import annotations
 
+import functools
 import math
+import os
 from typing import Callable, Dict, Tuple
 
 import numpy as np
@@ -420,7 +428,60 @@ def _groups(info, n):
     return np.asarray(gp, dtype=np.int64)
 
 
+def _rank_metric_device(kind, preds, info, param):
+    """ndcg / map / pre of fp32 device predictions through the counting
+    kernel (ops/cpp/rank_metric.hip), or None when this call is not the
+    kernel's: not a contiguous single-column fp32 HIP tensor, a group
+    above backend.gpu.RANK_METRIC_MAX_GROUP documents (the kernel's work
+    is quadratic in the group size), a library without the kernel, or
+    XGB_AMD_RANK_METRIC_HIP=0.  One host sync, of the per-group sum."""
+    import torch as _torch
+    if not (isinstance(preds, _torch.Tensor) and preds.is_cuda
+            and preds.dtype == _torch.float32 and preds.is_contiguous()
+            and (preds.dim() == 1 or (preds.dim() == 2
+                                      and preds.shape[1] == 1))
+            and info.labels is not None
+            and os.environ.get("XGB_AMD_RANK_METRIC_HIP", "1") != "0"):
+        return None
+    from . import ops as hip_ops
+    if not hasattr(hip_ops.load(), "gbt_rank_metric"):
+        return None
+    from .backend import gpu as gpu_backend
+    state = gpu_backend.rank_metric_state(info, preds.device)
+    if not state.eligible or state.n != preds.numel():
+        return None
+    minus = bool(kind != "pre" and param and param.endswith("-"))
+    topn = (int(param if kind == "pre" else param.rstrip("-")) if param
+            else 2 ** 31 - 1)
+    vals = gpu_backend.rank_metric_gpu(preds.detach().view(-1), state, kind,
+                                       topn, minus)
+    total = float(vals.sum())  # the one sync
+    if kind == "pre":
+        return _ratio(total, float(np.minimum(state.counts, topn).sum()))
+    sa, sv = collective.allreduce_sum_scalars([total, float(state.n_groups)])
+    return sa / max(sv, 1e-16)
+
+
+def _rank_hip(kind):
+    """Puts the device kernel in front of a numpy ranking metric, which
+    keeps serving every input the kernel does not take."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def call(preds, info, param=None):
+            import torch as _torch
+            val = _rank_metric_device(kind, preds, info, param)
+            if val is not None:
+                return val
+            if isinstance(preds, _torch.Tensor):
+                preds = preds.detach().cpu().numpy()
+            return fn(preds, info, param)
+        return call
+    return deco
+
+
 @register("ndcg")
+@_torch_ok
+@_rank_hip("ndcg")
 def ndcg(preds, info, param=None):
     topn = int(param.rstrip("-")) if param else 2 ** 31 - 1
     minus = bool(param and param.endswith("-"))
@@ -450,6 +511,8 @@ def ndcg(preds, info, param=None):
 
 
 @register("map")
+@_torch_ok
+@_rank_hip("map")
 def map_metric(preds, info, param=None):
     topn = int(param.rstrip("-")) if param else 2 ** 31 - 1
     minus = bool(param and param.endswith("-"))
@@ -475,6 +538,8 @@ def map_metric(preds, info, param=None):
 
 
 @register("pre")
+@_torch_ok
+@_rank_hip("pre")
 def precision_at(preds, info, param=None):
     topn = int(param) if param else 2 ** 31 - 1
     p = np.asarray(preds, dtype=np.float64).reshape(-1)

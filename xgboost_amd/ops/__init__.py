@@ -62,6 +62,12 @@ _SIGS = {
     "gbt_lambdarank": [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i,
                        _p, _p, _p],
     "gbt_lambdarank_tier_cap": [_i],
+    # kind, tier, scores, labels, group_ptr, work, n_work, k, part_off,
+    # partial
+    "gbt_rank_metric": [_i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p],
+    "gbt_rank_metric_slab": [_i],
+    # partial, part_off, scale, default, out, n_groups
+    "gbt_rank_metric_finish": [_p, _p, _p, _d, _p, _i, _p],
     "gbt_hist_cpu": [_p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i],
     "gbt_partition_cpu": [_p, _p, _i, _p, _i64, _i64, _i, _i, _i, _p, _i,
                           _i, _p],
@@ -143,6 +149,8 @@ def load() -> ctypes.CDLL:
         _lib.gbt_wt_arena_bytes.restype = _c.c_longlong
     if hasattr(_lib, "gbt_lambdarank_tier_cap"):
         _lib.gbt_lambdarank_tier_cap.restype = _c.c_int
+    if hasattr(_lib, "gbt_rank_metric_slab"):
+        _lib.gbt_rank_metric_slab.restype = _c.c_int
     if hasattr(_lib, "gbt_partition_cpu"):
         _lib.gbt_partition_cpu.restype = _c.c_longlong
     return _lib

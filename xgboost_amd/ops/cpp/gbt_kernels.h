@@ -182,6 +182,28 @@ void gbt_lambdarank(int metric, int tier, const float* scores,
 // Largest group a tier holds; 0 for an unknown tier.
 int gbt_lambdarank_tier_cap(int tier);
 
+// Ranking metrics by counting (rank_metric.hip), one launch per tier.
+// kind: 0 = ndcg, 1 = map, 2 = pre.  Tier 0 takes `work` as group ids of
+// 1..64 documents; every other tier takes {group, slab start} pairs, slab
+// starts being multiples of gbt_rank_metric_slab(tier).  Each work item
+// writes the fp64 sum of its documents' terms to
+// partial[part_off[group] + slab start / slab].
+void gbt_rank_metric(int kind, int tier, const float* scores,
+                     const float* labels,
+                     const long long* group_ptr,  // [G+1]
+                     const int32_t* work, int n_work, int k,
+                     const int32_t* part_off,     // [G+1]
+                     double* partial, hipStream_t stream);
+
+// Documents per work item of a tier; 0 for an unknown tier.
+int gbt_rank_metric_slab(int tier);
+
+// out[g] = sum of group g's partials in slab order, times scale[g]; dflt
+// where scale[g] <= 0; the bare sum when scale is null.
+void gbt_rank_metric_finish(const double* partial, const int32_t* part_off,
+                            const double* scale, double dflt, double* out,
+                            int n_groups, hipStream_t stream);
+
 void gbt_select_best(const double* gain, const int32_t* bins,
                      const uint8_t* dirs, const int64_t* lsum, int n_nodes,
                      int n_features, int64_t* out_best,
