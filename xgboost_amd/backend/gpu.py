@@ -1113,7 +1113,8 @@ class _ShapCsrPlan:
     DFS forest, the device CSR and col_map, and the per-chunk staging of
     the tile and of phi [G, U+1, rows] float64 (bias column preset)."""
 
-    def __init__(self, booster, dmat, lo, hi, used, col_map, want_ix):
+    def __init__(self, booster, dmat, lo, hi, used, col_map, want_ix,
+                 approx=False):
         from ..shap import _expected_value
         assert int(col_map.max(initial=-1)) < len(used)
         self.device = device = booster.device
@@ -1122,7 +1123,9 @@ class _ShapCsrPlan:
         self.g = booster.n_outputs
         self.base = booster._base_margin_value()
         self.fa = self.tab = None
-        if _has_categorical(booster, lo, hi):
+        if approx:
+            pass  # staging only: the Saabas walk has its own forest
+        elif _has_categorical(booster, lo, hi):
             depth = max((t.max_depth() for t in booster.trees[lo:hi]),
                         default=0)
             if want_ix or depth > 16 or self.u + 1 > 129:
@@ -1220,6 +1223,130 @@ def shap_interactions_csr_gpu(booster, dmat, lo: int, hi: int,
     return res
 
 
+# -- Saabas approx_contribs (shap_saabas.hip) ------------------------------
+
+# Split columns a block accumulates per pass over the trees, at most 127:
+# 79 keeps four 64-row blocks resident in a CU's 160 KB of LDS.  A forest
+# that uses more is walked once per window.
+_SHAP_APPROX_WINDOW = 79
+
+
+class _SaabasForest:
+    """What gbt_shap_saabas reads for trees [lo, hi) over an n_col-wide
+    matrix: the packed nodes without tree weights (as _host_contribs
+    takes them), the fp64 node means (computed on the device, once), the
+    used split columns with the feature -> slot map, and the fp64 bias of
+    every group (base margin + expected values, in tree order)."""
+
+    def __init__(self, booster, lo: int, hi: int, n_col: int, device):
+        from .. import ops as hip_ops
+        from ..shap import _expected_value, used_columns
+        lib = hip_ops.load()
+        trees = booster.trees[lo:hi]
+        if any(t.leaf_values is not None for t in trees):
+            raise ShapDeviceLimit("GPU approx_contribs: vector leaves")
+        for t in trees:
+            n = t.n_nodes
+            ids = np.arange(n)
+            inner = t.left[:n] != -1
+            for kid in (t.left[:n][inner], t.right[:n][inner]):
+                if not ((kid > ids[inner]) & (kid < n)).all():
+                    raise ShapDeviceLimit(
+                        "GPU approx_contribs: a child's id is not above "
+                        "its parent's")
+        self.used, col_map = used_columns(trees, n_col)
+        self.n_groups = g = int(booster.n_outputs)
+        self.fq = fq = _ForestQ(booster, range(lo, hi), device,
+                                fold_weights=False)
+        u = len(self.used)
+        self.slot_of = torch.from_numpy(col_map).to(device)
+        self.used_dev = torch.from_numpy(self.used.astype(np.int32)).to(device)
+        self.ident = torch.arange(u, dtype=torch.int32, device=device)
+        bias = np.full(g, booster._base_margin_value(), np.float64)
+        for t, k in zip(trees, booster.tree_info[lo:hi]):
+            bias[k] += _expected_value(t)
+        self.bias = torch.from_numpy(bias).to(device)
+        hess = (np.concatenate([t.sum_hess[:t.n_nodes] for t in trees])
+                if trees else np.zeros(0))
+        self.mean = torch.empty(len(hess), dtype=torch.float64, device=device)
+        lib.gbt_saabas_means(
+            hip_ops.ptr(fq.nodes), hip_ops.ptr(fq.tree_offsets),
+            hip_ops.ptr(torch.from_numpy(hess.astype(np.float32)).to(device)),
+            fq.n_trees, hip_ops.ptr(self.mean), hip_ops.stream())
+
+    def launch(self, X: torch.Tensor, n: int, row_stride: int,
+               col_stride: int, compact: bool, missing: float,
+               out: torch.Tensor) -> None:
+        """Store the contributions of n rows into the float32 out [n,
+        groups, C]: C = n_col + 1 on row-major X, or with `compact` C =
+        U + 1 on the staged feature-major tile."""
+        from .. import ops as hip_ops
+        fq = self.fq
+        u = len(self.used)
+        n_cols = out.shape[2]
+        assert out.dtype == torch.float32 and X.dtype == torch.float32
+        assert out.shape[:2] == (n, self.n_groups)
+        assert n_cols == (u if compact else self.slot_of.shape[0]) + 1
+        hip_ops.load().gbt_shap_saabas(
+            hip_ops.ptr(X), n, row_stride, col_stride, int(compact),
+            *_missing_args(missing), hip_ops.ptr(fq.nodes),
+            hip_ops.ptr(fq.tree_offsets), hip_ops.ptr(fq.cat_offsets),
+            hip_ops.ptr(fq.cat_bits), hip_ops.ptr(fq.tree_group),
+            hip_ops.ptr(self.mean), hip_ops.ptr(self.slot_of),
+            hip_ops.ptr(self.ident if compact else self.used_dev), u,
+            fq.n_trees, self.n_groups, n_cols, int(_SHAP_APPROX_WINDOW),
+            hip_ops.ptr(self.bias), hip_ops.ptr(out), hip_ops.stream())
+
+
+def _cached_saabas_forest(booster, lo: int, hi: int, n_col: int,
+                          device) -> _SaabasForest:
+    """One _SaabasForest kept on the booster, so repeated calls upload
+    nothing and do not recompute the node means."""
+    key = (len(booster.trees), str(device), lo, hi, n_col)
+    fc = booster.__dict__.setdefault("_saabas_cache", {})
+    if key not in fc:
+        fc.clear()  # another model state or range: drop the stale one
+        fc[key] = _SaabasForest(booster, lo, hi, n_col, device)
+    return fc[key]
+
+
+def shap_approx_gpu(booster, dmat, lo: int, hi: int,
+                    phi: np.ndarray) -> np.ndarray:
+    """approx_contribs (Saabas) on dense rows: float32 [n, groups, F + 1]
+    from gbt_shap_saabas.  No depth, column or categorical limit; only
+    vector leaves raise ShapDeviceLimit."""
+    n, n_groups, n_cols = phi.shape
+    device = booster.device
+    sf = _cached_saabas_forest(booster, lo, hi, n_cols - 1, device)
+    X = _device_rows(dmat, device).contiguous()
+    assert X.shape == (n, n_cols - 1)
+    out = torch.zeros((n, n_groups, n_cols), dtype=torch.float32,
+                      device=device)
+    sf.launch(X, n, n_cols - 1, 1, False, dmat.missing, out)
+    res = out.cpu().numpy()
+    return res[:, 0, :] if n_groups == 1 else res
+
+
+def shap_approx_csr_gpu(booster, dmat, lo: int, hi: int, used: np.ndarray,
+                        col_map: np.ndarray) -> np.ndarray:
+    """approx_contribs for a sparse CSR DMatrix in compact space, like
+    shap_csr_gpu: float32 [n, groups, U+1] on the host.  The walk reads
+    the staged tile as it is, feature-major."""
+    sf = _cached_saabas_forest(booster, lo, hi, dmat.num_col(),
+                               booster.device)
+    plan = _ShapCsrPlan(booster, dmat, lo, hi, used, col_map, False,
+                        approx=True)
+    n, u, g = plan.n, plan.u, plan.g
+    res = np.empty((n, g, u + 1), dtype=np.float32)
+    for r0, rows in plan.chunks(4 * u + 4 * g * (u + 1)):  # tile + out
+        tile = plan.tile(r0, rows)
+        out = torch.zeros((rows, g, u + 1), dtype=torch.float32,
+                          device=plan.device)
+        sf.launch(tile, rows, 1, rows, True, float("nan"), out)
+        res[r0:r0 + rows] = out.cpu().numpy()
+    return res
+
+
 def _cached_forest(booster, lo: int, hi: int, device) -> _ForestArrays:
     """Device forest SoA cached across predict calls (serving path:
     repeated inplace_predict uploads nothing but the rows)."""
@@ -1292,9 +1419,11 @@ class _ForestQ:
     value word is the leaf value at a leaf and otherwise the LOCAL split
     bin against `cuts` (bins kinds) or the split_cond bits (cuts=None,
     raw floats).  Vector-leaf trees get tree_group -1 and their rows in
-    leaf_vec; DART tree weights are folded into both leaf stores."""
+    leaf_vec; DART tree weights are folded into both leaf stores unless
+    `fold_weights` is False."""
 
-    def __init__(self, booster, idxs, device, cuts=None):
+    def __init__(self, booster, idxs, device, cuts=None,
+                 fold_weights: bool = True):
         from ..tree_model import local_split_bins
         idxs = list(idxs)
         trees = [booster.trees[i] for i in idxs]
@@ -1315,7 +1444,7 @@ class _ForestQ:
             o = int(offs[i])
             left = t.left[:n]
             leaf = left == -1
-            w = np.float32(booster._tw(idxs[i]))
+            w = np.float32(booster._tw(idxs[i]) if fold_weights else 1.0)
             rec = nodes[o:o + n]
             rec[:, 0] = left.view(np.uint32)
             rec[:, 1] = t.right[:n].view(np.uint32)

@@ -114,6 +114,14 @@ _SIGS = {
     # indptr, indices, values, row_begin, n_rows_chunk, col_map,
     # n_col_map, n_used, tile [n_used, n_rows_chunk]
     "gbt_csr_gather_columns": [_p, _p, _p, _i64, _i64, _p, _i, _i, _p, _p],
+    # nodes, tree_offsets, sum_hess, n_trees, mean_val
+    "gbt_saabas_means": [_p, _p, _p, _i, _p, _p],
+    # X, n_rows, row_stride, col_stride, compact, missing (2), forest (5:
+    # nodes, tree/cat offsets, cat bits, tree group), mean_val, slot_of,
+    # used, n_used, n_trees, n_groups, n_cols, window, bias, out
+    "gbt_shap_saabas": [_p, _i64, _i64, _i64, _i, _f, _i, _p, _p, _p, _p,
+                        _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
+    "gbt_shap_saabas_rows": [],
     "gbt_hist_mt": [_p, _p, _i, _p, _i, _p, _p, _i, _p, _i, _i,
                     _p, _p, _i, _i, _p, _p],
 }
@@ -151,6 +159,8 @@ def load() -> ctypes.CDLL:
         _lib.gbt_lambdarank_tier_cap.restype = _c.c_int
     if hasattr(_lib, "gbt_rank_metric_slab"):
         _lib.gbt_rank_metric_slab.restype = _c.c_int
+    if hasattr(_lib, "gbt_shap_saabas_rows"):
+        _lib.gbt_shap_saabas_rows.restype = _c.c_int
     if hasattr(_lib, "gbt_partition_cpu"):
         _lib.gbt_partition_cpu.restype = _c.c_longlong
     return _lib

@@ -14,17 +14,20 @@ SOURCES = ["hist.hip", "partition.hip", "evaluate.hip", "compress.hip",
            "predict.hip", "predict_bins.hip", "predict_csr.hip", "shap.hip",
            "shap_paths.hip", "shap_ix.hip", "shap_csr.hip",
            "driver.hip", "csr.hip", "gpair.hip", "mt_evaluate.hip",
-           "cpu_hist.cpp", "lambdarank.hip", "rank_metric.hip"]
+           "cpu_hist.cpp", "lambdarank.hip", "rank_metric.hip",
+           "shap_saabas.hip"]
 
 # Sources compiled on their own, with flags the other kernels were not
-# measured under: the ranking kernels keep the compiler from pairing fp32
-# operations into packed instructions and print the per-kernel resource
-# usage (registers, LDS, scratch, occupancy; profiles/lambdarank_mi355x.md).
+# measured under: the ranking and Saabas kernels keep the compiler from
+# pairing fp32 operations into packed instructions and print the per-kernel
+# resource usage (registers, LDS, scratch, occupancy;
+# profiles/lambdarank_mi355x.md, profiles/shap_approx_mi355x.md).
 _RANK_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
                "-Rpass-analysis=kernel-resource-usage"]
 OWN_FLAGS = {
     "lambdarank.hip": _RANK_FLAGS,
     "rank_metric.hip": _RANK_FLAGS,
+    "shap_saabas.hip": _RANK_FLAGS,
 }
 
 

@@ -204,6 +204,35 @@ void gbt_rank_metric_finish(const double* partial, const int32_t* part_off,
                             const double* scale, double dflt, double* out,
                             int n_groups, hipStream_t stream);
 
+// Saabas node means (shap_saabas.hip): mean_val[node] in fp64 for every
+// node of the packed forest, sum_hess a parallel [total_nodes] array.  A
+// child's id must be above its parent's.
+void gbt_saabas_means(const void* nodes, const int32_t* tree_offsets,
+                      const float* sum_hess, int n_trees, double* mean_val,
+                      hipStream_t stream);
+
+// approx_contribs by walking the packed forest (scalar leaves only).  X is
+// read at [row * row_stride + column * col_stride], the column being the
+// node's feature, or with compact != 0 its slot.  Stores the fp32
+// contributions of the n_used split columns to out[row, group, used[slot]]
+// and bias[group] to the last column; other cells of `out` [n_rows,
+// n_groups, n_cols] are left alone.  `window` columns are accumulated per
+// pass over the trees (clamped to 1..127).
+void gbt_shap_saabas(const float* X, int64_t n_rows, int64_t row_stride,
+                     int64_t col_stride, int compact, float missing_value,
+                     int missing_is_nan, const void* nodes,
+                     const int32_t* tree_offsets, const int32_t* cat_offsets,
+                     const uint32_t* cat_bits, const int32_t* tree_group,
+                     const double* mean_val,
+                     const int32_t* slot_of,  // [n_features] feature -> slot
+                     const int32_t* used,     // [n_used] slot -> column
+                     int n_used, int n_trees, int n_groups, int n_cols,
+                     int window, const double* bias, float* out,
+                     hipStream_t stream);
+
+// Rows of one block's tile in gbt_shap_saabas.
+int gbt_shap_saabas_rows();
+
 void gbt_select_best(const double* gain, const int32_t* bins,
                      const uint8_t* dirs, const int64_t* lsum, int n_nodes,
                      int n_features, int64_t* out_best,

@@ -4,8 +4,11 @@ Reference behavior: src/predictor/interpretability/shap.{cc,cu}
 (Quadrature-TreeSHAP) — we provide the same outputs (exact SHAP
 contributions, interactions, and the Saabas approximation for
 approx_contribs) via the classic path-dependent TreeSHAP recursion
-(Lundberg & Lee) on CPU; a HIP kernel accelerates pred_contribs on GPU
-(ops/cpp/shap.hip).
+(Lundberg & Lee) on CPU; HIP kernels run pred_contribs and
+pred_interactions on GPU (ops/cpp/shap_paths.hip, shap_ix.hip, shap.hip),
+and approx_contribs walks the forest there too (ops/cpp/shap_saabas.hip:
+no depth, column or categorical limit; only vector-leaf forests go to
+the host loop).
 
 Output convention matches xgboost: contribs shape [n, f+1] with the
 last column the bias (expected value incl. base_score); interactions
@@ -184,10 +187,11 @@ def shap_values(booster, dmat, iteration_range=(0, 0),
     n, f = X.shape
     phi = np.zeros((n, n_groups, f + 1), dtype=np.float64)
     phi[:, :, f] = booster._base_margin_value()
-    if booster.device.type == "cuda" and not approx:
+    if booster.device.type == "cuda":
         try:
-            from .backend.gpu import shap_gpu
-            return shap_gpu(booster, dmat, lo, hi, phi)
+            from .backend.gpu import shap_approx_gpu, shap_gpu
+            return (shap_approx_gpu if approx else shap_gpu)(
+                booster, dmat, lo, hi, phi)
         except ImportError:
             pass  # kernels not built, or a ShapDeviceLimit: exact host
     _host_contribs(booster.trees[lo:hi], booster.tree_info[lo:hi], X, phi,
@@ -348,12 +352,14 @@ def _expand_columns(compact: np.ndarray, used: np.ndarray, n_col: int,
 def _csr_contribs(booster, dmat, lo: int, hi: int, approx: bool):
     """Compact float32 contributions [n, groups, U+1] and `used`."""
     used, col_map = used_columns(booster.trees[lo:hi], dmat.num_col())
-    if booster.device.type == "cuda" and not approx:
+    if booster.device.type == "cuda":
         from .backend import gpu
+        route = gpu.shap_approx_csr_gpu if approx else gpu.shap_csr_gpu
         try:
-            return gpu.shap_csr_gpu(booster, dmat, lo, hi, used, col_map), used
+            return route(booster, dmat, lo, hi, used, col_map), used
         except gpu.ShapDeviceLimit:
-            pass  # categorical past the DFS caps / deep paths: exact host
+            pass  # categorical past the DFS caps / deep paths / vector
+            # leaves: exact host
     n, u = dmat.num_row(), len(used)
     X = _gather_used_columns(dmat.sparse_data(), used)
     phi = np.zeros((n, booster.n_outputs, u + 1), dtype=np.float64)
