@@ -29,6 +29,11 @@ _d = _c.c_double
 
 _SIGS = {
     "gbt_hist": [_p, _p, _i, _p, _p, _p, _i, _p, _i, _p, _p, _i, _i, _p, _i, _p, _p],
+    # gbt_hist with the slice count after use_shared
+    "gbt_hist_sliced": [_p, _p, _i, _p, _p, _p, _i, _p, _i, _p, _p, _i, _i,
+                        _p, _i, _i, _p, _p],
+    # n_groups, group features, group bins, bytes per bin, use_shared
+    "gbt_hist_slices": [_i, _i, _i, _i, _i],
     "gbt_partition": [_p, _p, _i, _p, _p, _i64, _p, _p, _p, _i, _p, _p, _p,
                       _p, _p, _p, _p, _p],
     # _ref is the single-wave reference behind the same arguments
@@ -151,6 +156,8 @@ def load() -> ctypes.CDLL:
     if hasattr(_lib, "gbt_driver_create"):
         _lib.gbt_driver_create.restype = _p
         _lib.gbt_grow_tree.restype = _c.c_int
+    if hasattr(_lib, "gbt_hist_slices"):
+        _lib.gbt_hist_slices.restype = _c.c_int
     if hasattr(_lib, "gbt_root_tasks_check"):
         _lib.gbt_root_tasks_check.restype = _c.c_int
     if hasattr(_lib, "gbt_wt_arena_bytes"):

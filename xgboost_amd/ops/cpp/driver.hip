@@ -247,16 +247,32 @@ bool WtGraphEnabled() {
 
 // hist wants FEWER, BIGGER tasks than partition: every block pays a
 // full LDS zero+flush of the group histogram, so rows/task must
-// amortize ~2*group_bins atomics (env GBT_HIST_TASKS to tune)
-constexpr long long kHistMinRows = 2048;
-long long HistTasksTarget() {
+// amortize ~2*group_bins atomics (env GBT_HIST_TASKS and
+// GBT_HIST_MIN_ROWS to tune; both are per block: a launch with S
+// feature slices divides the task target by S and multiplies the
+// minimum rows by S, see HistGeometry).
+//  - unsliced: one 112 KiB block per CU, so 256 tasks of >= 2048 rows
+//    (swept: 256 beats 512 by ~4% under whole-tree mode)
+//  - sliced: a slice's LDS lets several blocks share a CU, and two
+//    blocks per CU of >= 512 rows per slice measured best
+//    (profiles/r08_hist_slices.md)
+constexpr long long kHistMinRows = 2048, kHistMinRowsSliced = 512;
+constexpr long long kHistTasks = 256, kHistTasksSliced = 512;
+long long HistTasksTarget(bool sliced) {
   static long long v = [] {
     const char* e = getenv("GBT_HIST_TASKS");
-    long long t = e ? atoll(e) : 256;  // swept: 256 beats 512 by ~4%
-                                       // under whole-tree mode
-    return t >= 64 && t <= 16384 ? t : 256;
+    long long t = e ? atoll(e) : 0;
+    return t >= 64 && t <= 16384 ? t : 0;
   }();
-  return v;
+  return v ? v : (sliced ? kHistTasksSliced : kHistTasks);
+}
+long long HistMinRows(bool sliced) {
+  static long long v = [] {
+    const char* e = getenv("GBT_HIST_MIN_ROWS");
+    long long r = e ? atoll(e) : 0;
+    return r >= 256 && r <= 65536 ? r : 0;
+  }();
+  return v ? v : (sliced ? kHistMinRowsSliced : kHistMinRows);
 }
 
 // partition task granularity (whole-tree chain): every block makes one
@@ -763,6 +779,24 @@ struct GrowArgs {
   long long hist_row() const { return (long long)n_bins * 2; }
 };
 
+// Hist task geometry.  gbt_hist cuts every row chunk into `slices` blocks
+// by features (gbt_hist_slices, same inputs here as there), so the row
+// chunks grow by that factor: tasks x slices keeps to the block target,
+// each chunk's histogram is flushed once, and the padded grids shrink
+// with the task count.  One slice gives the unsliced geometry.
+struct HistTaskGeometry {
+  int slices;
+  long long min_rows, target_tasks;
+};
+HistTaskGeometry HistGeometry(const GrowArgs& a) {
+  const int s = gbt_hist_slices(a.n_groups,
+                                a.n_groups == 1 ? a.n_features : 32,
+                                a.max_group_bins, a.gidx8 != nullptr ? 1 : 2,
+                                a.use_shared);
+  return {s, HistMinRows(s > 1) * s,
+          std::max<long long>(1, HistTasksTarget(s > 1) / s)};
+}
+
 // host tree outputs (caller-sized to 2^(max_depth+1))
 struct TreeOut {
   int32_t* left;
@@ -1006,6 +1040,7 @@ struct WtChain {
   int n_root_tasks;
   long long root_rpt;
   int wt_max_htasks;
+  HistTaskGeometry hg;
   int n_ptasks;  // partition launch grid: sum over nodes of
                  // ceil(rows / rows-per-task)
   template <typename T>
@@ -1096,7 +1131,7 @@ int EnqueueChain(const GrowArgs& a, const WtChain& c, hipStream_t cs) {
                   d_dl, nullptr, nullptr, a.n_bins_feat_dev, d_cnt, cs);
     std::swap(cr, alt);
     hipLaunchKernelGGL(HistTaskGenKernel, dim3(1), dim3(256), 0, cs, d_cnt,
-                       d_desc, 0, kHistMinRows, HistTasksTarget(),
+                       d_desc, 0, c.hg.min_rows, c.hg.target_tasks,
                        c.wt_max_htasks, a.hist_tasks_dev, ps_next,
                        kp_arr + L + 1, so,
                        a.allreduce != nullptr ? 2 * cap_kids : 0,
@@ -1164,6 +1199,7 @@ GraphKey ChainKey(const GrowArgs& a, const WtChain& c) {
           (U)a.max_group_bins, (U)a.max_depth, (U)a.max_nodes_level,
           (U)a.wt_max_ptasks, (U)a.hist_tasks_cap, (U)c.n_root_tasks,
           (U)c.root_rpt, (U)PartMinRows(), (U)c.n_ptasks, (U)c.wt_max_htasks,
+          (U)c.hg.slices, (U)c.hg.min_rows, (U)c.hg.target_tasks,
           (U)a.has_mono(), db(a.reg_lambda), db(a.reg_alpha),
           db(a.max_delta_step), db(a.min_child_weight), db(a.gamma)};
 }
@@ -1177,11 +1213,12 @@ int GrowWholeTree(const GrowArgs& a, TreeOut* out,
   const WtArena& ar = c.ar;
   if ((long long)ar.total > a.wt_ws_bytes) return kErrArenaTooSmall;
   c.w = (char*)a.wt_ws;
-  c.root_rpt = RootRowsPerTask(a.n_rows, kHistMinRows, HistTasksTarget());
+  c.hg = HistGeometry(a);
+  c.root_rpt = RootRowsPerTask(a.n_rows, c.hg.min_rows, c.hg.target_tasks);
   c.n_root_tasks = RootTaskCount(a.n_rows, c.root_rpt);
   if (c.n_root_tasks > a.hist_tasks_cap) return kErrRootTasksCap;
   c.wt_max_htasks = (int)std::min<long long>(
-      std::min<long long>(a.n_rows / kHistMinRows, HistTasksTarget()) +
+      std::min<long long>(a.n_rows / c.hg.min_rows, c.hg.target_tasks) +
           a.max_nodes_level + 1,
       (long long)a.hist_tasks_cap);
   c.n_ptasks = (int)std::min<long long>(
@@ -1341,7 +1378,8 @@ int GrowPerLevel(const GrowArgs& a, TreeOut* out,
   PinnedRing& ring = ctx->ring;
   hipStream_t stream = a.stream;
   const long long hist_row = a.hist_row();
-  const long long hist_tasks = HistTasksTarget();
+  const HistTaskGeometry hg = HistGeometry(a);
+  const long long hist_tasks = hg.target_tasks;
   const bool has_mono = a.has_mono();
   Scales sc(a.g_scale, a.h_scale);
   {
@@ -1367,7 +1405,7 @@ int GrowPerLevel(const GrowArgs& a, TreeOut* out,
     // ---- root histogram: tasks host-generated (root segment is known)
     std::vector<Node*> nodes{&root};
     std::vector<BlockTask> tasks;
-    ChunkTasks(nodes, &tasks, kHistMinRows, hist_tasks);
+    ChunkTasks(nodes, &tasks, hg.min_rows, hist_tasks);
     const int slot = ring.next();
     size_t bytes = tasks.size() * sizeof(BlockTask);
     if (int e = ring.ensure(slot, bytes)) return e;
@@ -1528,11 +1566,11 @@ int GrowPerLevel(const GrowArgs& a, TreeOut* out,
     long long bound_total = 0;
     for (Node* nd : expand) bound_total += nd->seg_end - nd->seg_begin;
     int max_tasks = (int)std::min<long long>(
-        std::min<long long>(bound_total / kHistMinRows, hist_tasks) + kb + 1,
+        std::min<long long>(bound_total / hg.min_rows, hist_tasks) + kb + 1,
         a.hist_tasks_cap);
     hipLaunchKernelGGL(HistTaskGenKernel, dim3(1), dim3(256), 0, stream,
                        cnt_dev, (const int32_t*)(d + off_desc), kb,
-                       kHistMinRows, hist_tasks, max_tasks, a.hist_tasks_dev,
+                       hg.min_rows, hist_tasks, max_tasks, a.hist_tasks_dev,
                        eval_ps, nullptr, nullptr, 0, nullptr);
     HIP_CHECK(hipMemsetAsync(next_pool, 0,
                              (size_t)kb * hist_row * sizeof(int64_t), stream));

@@ -34,6 +34,29 @@ void gbt_hist(const uint8_t* gidx8, const uint16_t* gidx16,
               int64_t* node_sums,  // [n_slots,2] or null: per-slot pair sums
               hipStream_t stream);
 
+// Feature slices of the register-metadata histogram kernel (use_shared
+// >= 2): how many blocks share one row chunk, each building a contiguous
+// part of every group's features.  Inputs are the launch geometry: group
+// count, features and bins of the (widest) group, bytes per stored bin
+// and the launch mode.  1 for the other kernels.  gbt_hist launches with
+// this count, and whoever makes its tasks sizes them by it: target tasks
+// / slices, minimum rows * slices (see HistTaskGeometry in driver.hip).
+int gbt_hist_slices(int n_groups, int group_features, int group_bins,
+                    int bin_bytes, int use_shared);
+
+// gbt_hist with an explicit slice count (clamped to the load units of a
+// group; ignored by the kernels that do not slice).  Results do not
+// depend on it.
+void gbt_hist_sliced(const uint8_t* gidx8, const uint16_t* gidx16,
+                     int n_features, const int32_t* qgpair,
+                     const int32_t* ridx, const BlockTask* tasks, int n_tasks,
+                     int64_t* out_hist, int n_bins,
+                     const int32_t* feat_group_start,
+                     const int32_t* bin_group_start, int n_groups,
+                     int max_group_bins, const int32_t* cut_ptrs,
+                     int use_shared, int slices, int64_t* node_sums,
+                     hipStream_t stream);
+
 void gbt_partition(const uint8_t* gidx8, const uint16_t* gidx16,
                    int n_features,
                    const uint8_t* gidx8_col,   // optional feature-major

@@ -4,23 +4,32 @@
 // re-designed for MI355X rather than translated:
 //  - LDS-privatized per-workgroup histogram covering a whole feature
 //    group (160 KiB LDS/CU lets one group hold up to ~9K bins at
-//    16 B/bin; Higgs 28x256=7168 bins fits in a single group, so the
-//    entire node histogram lives in LDS and is flushed once).
-//  - 64-wide wavefronts; 1024-thread blocks (16 waves/CU at the
-//    1-block LDS occupancy) hide ds_add latency.
+//    16 B/bin; Higgs 28x256=7168 bins fits in a single group), flushed
+//    to global memory once per block.
+//  - 64-wide wavefronts; 512-thread blocks on the register-metadata
+//    kernel (HistKernelReg), 1024 on the generic one (HistKernel).
 //  - int32 quantized gradients accumulated into int64 bins via
 //    atomicAdd(u64) — ds_add_u64 on LDS, global_atomic_add_u64 on HBM:
 //    deterministic regardless of ordering (two's complement wraparound
 //    is exact for signed fixed-point).
 //  - blockIdx.x enumerates (node, row-chunk) tasks; blockIdx.y the
-//    feature group (grid-filling: tasks are sized so n_tasks >= ~2048
-//    when rows allow, covering 256 CUs across 8 XCDs).
+//    feature group, and on HistKernelReg (group, feature slice): with S
+//    slices a block zeroes, accumulates and flushes only its slice's bins
+//    of the group, so a row chunk's histogram is still flushed once in
+//    total while the chunk is S times larger — S times fewer global
+//    flush atomics at the same block count.  S comes from
+//    gbt_hist_slices(); the drivers size their tasks by the same S.
 #include "gbt_kernels.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 #ifndef GBT_HIST_BLOCK
 #define GBT_HIST_BLOCK 1024
+#endif
+// slices gbt_hist_slices() returns for the measured shape class
+#ifndef GBT_HIST_DEFAULT_SLICES
+#define GBT_HIST_DEFAULT_SLICES 4
 #endif
 #define GBT_HIST_MAX_F 1024  // per-block staged feature metadata cap
 
@@ -181,6 +190,16 @@ __global__ __launch_bounds__(GBT_HIST_BLOCK) void HistKernel(
 // packed 32-bit loads (4 features per load) instead of 28 byte loads.
 // Atomic count is unchanged — this attacks the ISSUE-slot bound the
 // round-1 PMC ladder identified (bank conflicts were only ~6%).
+//
+// Feature slices: blockIdx.y = group * slices + slice.  A group's load
+// units (one 32-bit load on the kVec path, one feature otherwise) are
+// cut into min(slices, units) contiguous runs as evenly as possible; a
+// block owns one run: it loads only those dwords of the row and zeroes,
+// accumulates and flushes only those features' bins, held in LDS
+// relative to the slice's first bin.  kGF bounds the features of a
+// slice (the launcher picks it from the slice count).  Blocks of a
+// slice index past the group's unit count, and blocks of the grid.x
+// padding (blockIdx.x >= n_tasks), return at once.
 template <typename BinT, int kGF, bool kVec>
 __global__ __launch_bounds__(GBT_HIST_BLOCK) void HistKernelReg(
     const BinT* __restrict__ gidx, int n_features,
@@ -188,85 +207,95 @@ __global__ __launch_bounds__(GBT_HIST_BLOCK) void HistKernelReg(
     const BlockTask* __restrict__ tasks,
     int64_t* __restrict__ out_hist, int n_bins,
     const int32_t* __restrict__ feat_group_start,
-    const int32_t* __restrict__ bin_group_start,
     const int32_t* __restrict__ cut_ptrs,
-    int64_t* __restrict__ node_sums) {
+    int64_t* __restrict__ node_sums, int n_tasks, int slices) {
+  if ((int)blockIdx.x >= n_tasks) return;
   const BlockTask task = tasks[blockIdx.x];
   if (task.row_begin >= task.row_end) return;
-  const int group = blockIdx.y;
+  constexpr int kLanes = kVec ? 4 / (int)sizeof(BinT) : 1;
+  const int group = (int)blockIdx.y / slices;
+  const int slice = (int)blockIdx.y - group * slices;
   const int f_begin = feat_group_start[group];
   const int gf = feat_group_start[group + 1] - f_begin;
-  const int bin_begin = bin_group_start[group];
-  const int group_bins = bin_group_start[group + 1] - bin_begin;
+  const int units = (gf + kLanes - 1) / kLanes;
+  const int n_slices = min(slices, units);
+  if (slice >= n_slices) return;
+  // this block's features of the group: [sf_begin, sf_begin + sf)
+  const int sf_begin = min(gf, slice * units / n_slices * kLanes);
+  const int sf = min(
+      kGF, min(gf, (slice + 1) * units / n_slices * kLanes) - sf_begin);
+  const int bin_begin = cut_ptrs[f_begin + sf_begin];
+  const int slice_bins = cut_ptrs[f_begin + sf_begin + sf] - bin_begin;
 
-  unsigned meta[kGF];  // (group-rel start << 16) | width, both < 65536
+  unsigned meta[kGF];  // (slice-rel start << 16) | width, both < 65536
 #pragma unroll
   for (int f = 0; f < kGF; ++f) {
-    if (f < gf) {
-      const int c0 = cut_ptrs[f_begin + f];
+    if (f < sf) {
+      const int c0 = cut_ptrs[f_begin + sf_begin + f];
       meta[f] = ((unsigned)(c0 - bin_begin) << 16)
-                | (unsigned)(cut_ptrs[f_begin + f + 1] - c0);
+                | (unsigned)(cut_ptrs[f_begin + sf_begin + f + 1] - c0);
     } else {
       meta[f] = 0;
     }
   }
 
   extern __shared__ unsigned long long smem[];
-  for (int i = threadIdx.x; i < group_bins * 2; i += blockDim.x) {
+  for (int i = threadIdx.x; i < slice_bins * 2; i += blockDim.x) {
     smem[i] = 0ULL;
   }
   __syncthreads();
 
   int64_t* hist_g = out_hist + (size_t)task.out_slot * n_bins * 2;
-  const bool do_sums = node_sums != nullptr && group == 0;
+  const bool do_sums = node_sums != nullptr && blockIdx.y == 0;
   long long sum_g = 0, sum_h = 0;
-  for (int i = task.row_begin + (int)threadIdx.x; i < task.row_end;
-       i += blockDim.x) {
-    const int row = ridx[i];
-    const long long g = qgpair[2 * (size_t)row];
-    const long long h = qgpair[2 * (size_t)row + 1];
+  // One row in registers: its gradient pair and kW words of bins — on
+  // the kVec path dword-packed loads of 4 (u8) / 2 (u16) features (the
+  // launcher guarantees rows stay 4-aligned; slices begin on a load
+  // unit), otherwise one feature per word.
+  constexpr int kW = kGF / kLanes;
+  auto load_row = [&](int row, unsigned (&w)[kW], int& g, int& h) {
+    g = qgpair[2 * (size_t)row];
+    h = qgpair[2 * (size_t)row + 1];
+    const BinT* rowbins =
+        gidx + (size_t)row * n_features + f_begin + sf_begin;
+#pragma unroll
+    for (int u = 0; u < kW; ++u) {
+      w[u] = 0;
+      if (kLanes * u < sf) {
+        w[u] = kVec ? ((const unsigned*)rowbins)[u] : (unsigned)rowbins[u];
+      }
+    }
+  };
+  auto add_row = [&](const unsigned (&w)[kW], long long g, long long h) {
     if (do_sums) {
       sum_g += g;
       sum_h += h;
     }
-    const BinT* rowbins = gidx + (size_t)row * n_features + f_begin;
-    if (kVec) {
-      // dword-packed bin loads: 4 (u8) / 2 (u16) features per 32-bit
-      // load (launcher guarantees rows stay 4-aligned)
-      constexpr int kLanes = 4 / (int)sizeof(BinT);
-      const unsigned* rowu = (const unsigned*)rowbins;
 #pragma unroll
-      for (int f4 = 0; f4 < kGF / kLanes; ++f4) {
-        if (kLanes * f4 >= gf) break;
-        const unsigned packed = rowu[f4];
+    for (int u = 0; u < kW; ++u) {
+      if (kLanes * u >= sf) break;
 #pragma unroll
-        for (int j = 0; j < kLanes; ++j) {
-          const int f = kLanes * f4 + j;
-          const unsigned m = meta[f];
-          const int local = (int)((packed >> (8 * (int)sizeof(BinT) * j))
-                                  & (sizeof(BinT) == 1 ? 0xFFu : 0xFFFFu));
-          if (local >= (int)(m & 0xFFFFu)) continue;
-          const int sbin = (int)(m >> 16) + local;
-          atomicAdd(&smem[2 * sbin], (unsigned long long)g);
-          atomicAdd(&smem[2 * sbin + 1], (unsigned long long)h);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int f = 0; f < kGF; ++f) {
-        if (f >= gf) break;
-        const unsigned m = meta[f];
-        const int local = (int)rowbins[f];
-        if (local >= (int)(m & 0xFFFFu)) continue;
+      for (int j = 0; j < kLanes; ++j) {
+        const unsigned m = meta[kLanes * u + j];
+        const int local = (int)((w[u] >> (8 * (int)sizeof(BinT) * j))
+                                & (sizeof(BinT) == 1 ? 0xFFu : 0xFFFFu));
+        if (local >= (int)(m & 0xFFFFu)) continue;  // missing sentinel
         const int sbin = (int)(m >> 16) + local;
         atomicAdd(&smem[2 * sbin], (unsigned long long)g);
         atomicAdd(&smem[2 * sbin + 1], (unsigned long long)h);
       }
     }
+  };
+  for (int i = task.row_begin + (int)threadIdx.x; i < task.row_end;
+       i += blockDim.x) {
+    unsigned w[kW];
+    int g, h;
+    load_row(ridx[i], w, g, h);
+    add_row(w, g, h);
   }
 
   __syncthreads();
-  for (int i = threadIdx.x; i < group_bins * 2; i += blockDim.x) {
+  for (int i = threadIdx.x; i < slice_bins * 2; i += blockDim.x) {
     const unsigned long long v = smem[i];
     if (v != 0ULL) {
       atomicAdd((unsigned long long*)&hist_g[2 * bin_begin + i], v);
@@ -301,6 +330,66 @@ __global__ __launch_bounds__(GBT_HIST_BLOCK) void HistKernelReg(
   }
 }
 
+// Slice policy.  Measured on MI355X at one shape class only
+// (profiles/r08_hist_slices.md): one LDS group of u8 bins whose flush is
+// large against its row work, 28 features x 256 bins.  Everything else
+// keeps one slice until it is measured.  Env GBT_HIST_SLICES overrides
+// the choice for every register-kernel launch (read once per process);
+// either way the result is at most the load units of the widest group.
+extern "C" int gbt_hist_slices(int n_groups, int group_features,
+                               int group_bins, int bin_bytes,
+                               int use_shared) {
+  static int env = [] {
+    const char* e = getenv("GBT_HIST_SLICES");
+    const int v = e ? atoi(e) : 0;
+    return v >= 1 && v <= 64 ? v : 0;
+  }();
+  static int use_reg = [] {
+    const char* e = getenv("GBT_HIST_REG");
+    return e ? atoi(e) : 1;
+  }();
+  if (!use_reg || use_shared < 2 || (bin_bytes != 1 && bin_bytes != 2))
+    return 1;
+  int s = env;
+  if (s == 0) {
+    s = (n_groups == 1 && bin_bytes == 1 && group_features >= 16 &&
+         group_features <= 32 && group_bins >= 4096)
+            ? GBT_HIST_DEFAULT_SLICES : 1;
+  }
+  const int lanes = use_shared >= 3 ? 4 / bin_bytes : 1;
+  const int gf = group_features < 32 ? group_features : 32;
+  const int units = (gf + lanes - 1) / lanes;
+  return s < units ? s : (units > 1 ? units : 1);
+}
+
+namespace {
+
+template <typename BinT, bool kVec>
+void LaunchHistReg(int slice_features, dim3 grid, dim3 block, size_t shmem,
+                   hipStream_t stream, const BinT* gidx, int n_features,
+                   const int32_t* qgpair, const int32_t* ridx,
+                   const BlockTask* tasks, int64_t* out_hist, int n_bins,
+                   const int32_t* feat_group_start, const int32_t* cut_ptrs,
+                   int64_t* node_sums, int n_tasks, int slices) {
+#define GBT_HIST_REG_LAUNCH(GF)                                              \
+  hipLaunchKernelGGL((HistKernelReg<BinT, GF, kVec>), grid, block, shmem,    \
+                     stream, gidx, n_features, qgpair, ridx, tasks,          \
+                     out_hist, n_bins, feat_group_start, cut_ptrs,           \
+                     node_sums, n_tasks, slices)
+  if (slice_features <= 4) {
+    GBT_HIST_REG_LAUNCH(4);
+  } else if (slice_features <= 8) {
+    GBT_HIST_REG_LAUNCH(8);
+  } else if (slice_features <= 16) {
+    GBT_HIST_REG_LAUNCH(16);
+  } else {
+    GBT_HIST_REG_LAUNCH(32);
+  }
+#undef GBT_HIST_REG_LAUNCH
+}
+
+}  // namespace
+
 extern "C" void gbt_hist(const uint8_t* gidx8, const uint16_t* gidx16,
                          int n_features, const int32_t* qgpair,
                          const int32_t* ridx, const BlockTask* tasks,
@@ -310,6 +399,22 @@ extern "C" void gbt_hist(const uint8_t* gidx8, const uint16_t* gidx16,
                          int max_group_bins, const int32_t* cut_ptrs,
                          int use_shared, int64_t* node_sums,
                          hipStream_t stream) {
+  const int slices = gbt_hist_slices(
+      n_groups, n_groups == 1 ? n_features : 32, max_group_bins,
+      gidx8 != nullptr ? 1 : 2, use_shared);
+  gbt_hist_sliced(gidx8, gidx16, n_features, qgpair, ridx, tasks, n_tasks,
+                  out_hist, n_bins, feat_group_start, bin_group_start,
+                  n_groups, max_group_bins, cut_ptrs, use_shared, slices,
+                  node_sums, stream);
+}
+
+extern "C" void gbt_hist_sliced(
+    const uint8_t* gidx8, const uint16_t* gidx16, int n_features,
+    const int32_t* qgpair, const int32_t* ridx, const BlockTask* tasks,
+    int n_tasks, int64_t* out_hist, int n_bins,
+    const int32_t* feat_group_start, const int32_t* bin_group_start,
+    int n_groups, int max_group_bins, const int32_t* cut_ptrs, int use_shared,
+    int slices, int64_t* node_sums, hipStream_t stream) {
   static int block_env = [] {
     const char* e = getenv("GBT_HIST_BLOCK_SIZE");
     int v = e ? atoi(e) : 0;
@@ -334,33 +439,69 @@ extern "C" void gbt_hist(const uint8_t* gidx8, const uint16_t* gidx16,
     return e ? atoi(e) : 1;
   }();
   if (use_reg && use_shared >= 2) {
+    // host-side bounds of the slice geometry the kernel derives per
+    // group: a group has at most max_gf features, so at most units_max
+    // load units, and an even cut into s runs gives runs of at most
+    // ceil(units_max / s) units
+    const int lanes = use_shared >= 3 ? (gidx8 != nullptr ? 4 : 2) : 1;
+    const int max_gf = std::min(n_groups == 1 ? n_features : 32, 32);
+    const int units_max = (max_gf + lanes - 1) / lanes;
+    const int s = std::max(1, std::min(slices, units_max));
+    // one slice is the unsliced launch: kGF = 32, the group's bins
+    const int slice_features = s == 1 ? 32 : (units_max + s - 1) / s * lanes;
     dim3 rgrid(n_tasks, n_groups);
+    if (s > 1) {
+      // Workgroups go to the 8 XCDs round-robin in linear id order
+      // (x fastest).  With grid.x a multiple of 8, block (x, y) lands
+      // on XCD x % 8 for every y: the slices of one row chunk share an
+      // L2, so the chunk's rows are fetched from HBM once.  Env
+      // GBT_HIST_XCD_ALIGN=0 drops the padding for A/B.
+      static int xcd_align = [] {
+        const char* e = getenv("GBT_HIST_XCD_ALIGN");
+        return e ? atoi(e) : 1;
+      }();
+      rgrid = dim3(xcd_align ? (n_tasks + 7) / 8 * 8 : n_tasks,
+                   n_groups * s);
+      // a u8 feature has at most 256 bins (its local ids and the
+      // missing sentinel fit a byte), which bounds a slice's bins
+      // without the host knowing the cuts; u16 keeps the group's size
+      // (sized by the kGF LaunchHistReg picks, which caps the kernel's
+      // slice)
+      if (gidx8 != nullptr) {
+        const int kgf = slice_features <= 4 ? 4 : slice_features <= 8 ? 8
+                        : slice_features <= 16 ? 16 : 32;
+        shmem = (size_t)std::min(max_group_bins, kgf * 256) * 2 *
+                sizeof(int64_t);
+      }
+    }
     dim3 rblock(reg_block);
     if (gidx8 != nullptr) {
       if (use_shared >= 3) {
-        hipLaunchKernelGGL((HistKernelReg<uint8_t, 32, true>), rgrid,
-                           rblock, shmem, stream, gidx8, n_features, qgpair,
-                           ridx, tasks, out_hist, n_bins, feat_group_start,
-                           bin_group_start, cut_ptrs, node_sums);
+        LaunchHistReg<uint8_t, true>(slice_features, rgrid, rblock, shmem,
+                                     stream, gidx8, n_features, qgpair, ridx,
+                                     tasks, out_hist, n_bins,
+                                     feat_group_start, cut_ptrs, node_sums,
+                                     n_tasks, s);
       } else {
-        hipLaunchKernelGGL((HistKernelReg<uint8_t, 32, false>), rgrid,
-                           rblock, shmem, stream, gidx8, n_features, qgpair,
-                           ridx, tasks, out_hist, n_bins, feat_group_start,
-                           bin_group_start, cut_ptrs, node_sums);
+        LaunchHistReg<uint8_t, false>(slice_features, rgrid, rblock, shmem,
+                                      stream, gidx8, n_features, qgpair, ridx,
+                                      tasks, out_hist, n_bins,
+                                      feat_group_start, cut_ptrs, node_sums,
+                                      n_tasks, s);
       }
     } else {
       if (use_shared >= 3) {
-        hipLaunchKernelGGL((HistKernelReg<uint16_t, 32, true>), rgrid,
-                           rblock, shmem, stream, gidx16, n_features,
-                           qgpair, ridx, tasks, out_hist, n_bins,
-                           feat_group_start, bin_group_start, cut_ptrs,
-                           node_sums);
+        LaunchHistReg<uint16_t, true>(slice_features, rgrid, rblock, shmem,
+                                      stream, gidx16, n_features, qgpair,
+                                      ridx, tasks, out_hist, n_bins,
+                                      feat_group_start, cut_ptrs, node_sums,
+                                      n_tasks, s);
       } else {
-        hipLaunchKernelGGL((HistKernelReg<uint16_t, 32, false>), rgrid,
-                           rblock, shmem, stream, gidx16, n_features,
-                           qgpair, ridx, tasks, out_hist, n_bins,
-                           feat_group_start, bin_group_start, cut_ptrs,
-                           node_sums);
+        LaunchHistReg<uint16_t, false>(slice_features, rgrid, rblock, shmem,
+                                       stream, gidx16, n_features, qgpair,
+                                       ridx, tasks, out_hist, n_bins,
+                                       feat_group_start, cut_ptrs, node_sums,
+                                       n_tasks, s);
       }
     }
     return;
