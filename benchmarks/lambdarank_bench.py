@@ -9,6 +9,14 @@ scores from a few boosting rounds.  Shape (b): about 1M documents in
 seeded log-normal group sizes clipped to 1..1251, same scores.
 --tiers also times the kernel's alternative block shapes.
 
+--slab times the slab tier instead (lambdarank_slab.hip, groups above
+2048 documents): one group of 2^12 .. 2^18 documents, the kernel against
+the torch path for the three objectives, which sets LAMBDARANK_MAX_GROUP;
+the slab shapes; and shape (m), 1M documents in groups of 100 with two
+groups of 4096 among them (0.8% of the documents), against the torch path
+that a data set with one such group took whole before this tier, with the
+same groups of 100 alone beside it.
+
 --metrics times the ranking metrics instead (rank_metric.hip): Booster.
 eval_set per call at shape (a) for ndcg, map@10 and pre@10, the kernel
 against XGB_AMD_RANK_METRIC_HIP=0; the kernel's block shapes at shape (b)
@@ -100,6 +108,66 @@ def tiers(name, shape, info, preds, calls, warmup):
                           "median_ms": round(float(np.median(t)), 4),
                           "min_ms": round(float(np.min(t)), 4),
                           "max_ms": round(float(np.max(t)), 4)}), flush=True)
+
+
+SLAB_SHAPES = {"256x1": (256, 0), "256x2": (512, 1), "256x4": (1024, 2),
+               "256x8": (2048, 3)}
+
+
+def slab_shapes(name, shape, info, preds, calls, warmup):
+    """The slab tier with each block shape, alternated."""
+    default = gpu_backend.LAMBDARANK_SLAB
+    objs = {}
+    try:
+        for v, sl in SLAB_SHAPES.items():
+            gpu_backend.LAMBDARANK_SLAB = sl
+            objs[v] = create_objective(name)
+            _call(objs[v], preds, info, "1")  # builds the state
+    finally:
+        gpu_backend.LAMBDARANK_SLAB = default
+    times = {v: [] for v in objs}
+    for i in range(warmup + calls):
+        for v, obj in objs.items():
+            ms, _ = _call(obj, preds, info, "1")
+            if i >= warmup:
+                times[v].append(ms)
+    for v, t in times.items():
+        _report(f"{name} kernel {shape}", {"slab": v}, t, calls)
+
+
+def slab_mode(y, ybin, preds, calls, warmup):
+    names = ("rank:ndcg", "rank:map", "rank:pairwise")
+    saved = gpu_backend.LAMBDARANK_MAX_GROUP
+    gpu_backend.LAMBDARANK_MAX_GROUP = 1 << 18
+    try:
+        for m in (12, 14, 16, 18):
+            n = 1 << m
+            for name in names:
+                lab = ybin if name == "rank:map" else y
+                ab(name, f"one group 2^{m}", _info(lab[:n], [n]),
+                   preds[:n].contiguous(), calls, warmup)
+        for m in (12, 16):
+            n = 1 << m
+            for name in ("rank:ndcg", "rank:map"):
+                lab = ybin if name == "rank:map" else y
+                slab_shapes(name, f"one group 2^{m}", _info(lab[:n], [n]),
+                            preds[:n].contiguous(), calls, warmup)
+    finally:
+        gpu_backend.LAMBDARANK_MAX_GROUP = saved
+    n = preds.shape[0]
+    n100 = (n - 2 * 4096) // 100
+    sizes_m = np.full(n100 + 2, 100)
+    sizes_m[[n100 // 3, 2 * n100 // 3]] = 4096
+    nm = int(sizes_m.sum())
+    for name in names:
+        lab = ybin if name == "rank:map" else y
+        ab(name, "m", _info(lab[:nm], sizes_m), preds[:nm].contiguous(),
+           calls, warmup)
+        ab(name, "m, groups of 100 alone", _info(lab[:n100 * 100],
+                                                 np.full(n100, 100)),
+           preds[:n100 * 100].contiguous(), calls, warmup)
+    slab_shapes("rank:ndcg", "m", _info(y[:nm], sizes_m),
+                preds[:nm].contiguous(), calls, warmup)
 
 
 def _report(bench, extra, t, calls):
@@ -201,6 +269,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--tiers", action="store_true")
     ap.add_argument("--metrics", action="store_true")
+    ap.add_argument("--slab", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark measures the GPU"
 
@@ -233,6 +302,9 @@ def main():
             info, p = shapes[shape]
             metric_shapes(shape, info, p.view(-1), args.calls, args.warmup)
         metric_cap(args.calls, args.warmup)
+        return
+    if args.slab:
+        slab_mode(y, ybin, preds, args.calls, args.warmup)
         return
     for name in ("rank:ndcg", "rank:map", "rank:pairwise"):
         info = _info(ybin, sizes_a) if name == "rank:map" else shapes["a"][0]

@@ -1699,23 +1699,47 @@ def predict_margin_csr_gpu(booster, dmat, out: Optional[torch.Tensor],
 
 
 # ---------------------------------------------------------------------------
-# LambdaMART gradients (lambdarank.hip)
+# LambdaMART gradients (lambdarank.hip, lambdarank_slab.hip)
 
-LAMBDARANK_MAX_GROUP = 2048  # kMaxGroup: the largest tier's LDS capacity
+# The largest group the kernel path takes.  The slab tier ranks by counting,
+# which is quadratic in the group size: this is the largest power of two at
+# which one group on the kernel still beats the torch path for all three
+# objectives (profiles/lambdarank_mi355x.md).  A data set with a larger
+# group takes the torch path whole.
+LAMBDARANK_MAX_GROUP = 1 << 16
+# kMaxGroup of lambdarank.hip: the largest LDS tier's capacity.  Longer
+# groups go to the slab tier.
+LAMBDARANK_LDS_MAX_GROUP = 2048
 LAMBDARANK_METRICS = {"ndcg": 0, "map": 1, "pairwise": 2}
 # tier name -> (largest group, kernel tier id).  The kernel has two block
 # shapes for "mid" (ids 1/2: 128/256 threads) and for "large" (ids 3/4:
 # 256/512 threads); the ids here are the ones measured faster: 128 and
 # 512 threads (profiles/lambdarank_mi355x.md).
 LAMBDARANK_TIERS = {"wave": (64, 0), "mid": (256, 1), "large": (2048, 4)}
+# Slab tier: (documents per work item, kernel shape id).  256 threads with
+# 1, 2, 4 or 8 documents each (ids 0..3); the one measured fastest
+# (profiles/lambdarank_mi355x.md).
+LAMBDARANK_SLAB = (256, 0)
+# Most row-share entries (two doubles each) the slab tier may ask for:
+# items(group) * min(k, n) summed over its groups.  128 MiB; the default
+# k = 32 needs 8192 entries for a group of 2^16.
+LAMBDARANK_SLAB_ROWS = 1 << 23
+LAMBDARANK_DEFAULT_K = 32
 
 
-def lambdarank_schedule(group_ptr: np.ndarray) -> dict:
-    """Work lists for the ranking kernel, plain numpy: every non-empty
-    group's id in the list of the smallest tier that holds it, largest
-    groups first within a tier (the long blocks start first; ties keep
-    group order).  `eligible` is False when a group exceeds
-    LAMBDARANK_MAX_GROUP or the pointer does not cover [0, N) in order."""
+def lambdarank_schedule(group_ptr: np.ndarray, k: int = LAMBDARANK_DEFAULT_K,
+                        slab: int = LAMBDARANK_SLAB[0]) -> dict:
+    """Work lists for the ranking kernels, plain numpy.  `lists`: every
+    non-empty group's id of up to LAMBDARANK_LDS_MAX_GROUP documents in
+    the list of the smallest tier that holds it, largest groups first
+    within a tier (the long blocks start first; ties keep group order).
+    `slab`: the longer groups.  `items` has one (group, slab start) row
+    per `slab` documents, largest groups first, a group's slabs in order;
+    per group id, `item_off` is its first item slot, `doc_off` its first
+    slot in the by-rank scratch and `row_off` its first row-share entry,
+    items * min(k, n) of them per group.  `eligible` is False when a group
+    exceeds LAMBDARANK_MAX_GROUP, the row shares exceed
+    LAMBDARANK_SLAB_ROWS or the pointer does not cover [0, N) in order."""
     gp = np.asarray(group_ptr, np.int64).reshape(-1)
     cnt = np.diff(gp)
     max_group = int(cnt.max()) if cnt.size else 0
@@ -1728,7 +1752,27 @@ def lambdarank_schedule(group_ptr: np.ndarray) -> dict:
         ids = ids[np.argsort(-cnt[ids], kind="stable")]
         lists[name] = ids.astype(np.int32)
         lo = cap
-    return {"lists": lists, "max_group": max_group, "eligible": ok}
+    big = cnt > LAMBDARANK_LDS_MAX_GROUP
+    n_items = np.where(big, -(-cnt // slab), 0)
+    ids = np.nonzero(big)[0]
+    ids = ids[np.argsort(-cnt[ids], kind="stable")]
+    reps = n_items[ids]
+    first = np.cumsum(reps) - reps  # index of each group's first item
+    item_start = (np.arange(int(reps.sum())) - np.repeat(first, reps)) * slab
+    rows = n_items * np.minimum(cnt, max(int(k), 0))
+
+    def offsets(v):
+        return np.concatenate([[0], np.cumsum(v)]).astype(np.int64)
+
+    slab_entry = {
+        "items": np.stack([np.repeat(ids, reps), item_start],
+                          1).astype(np.int32),
+        "item_off": offsets(n_items).astype(np.int32),
+        "doc_off": offsets(np.where(big, cnt, 0)),
+        "row_off": offsets(rows)}
+    ok = ok and int(slab_entry["row_off"][-1]) <= LAMBDARANK_SLAB_ROWS
+    return {"lists": lists, "slab": slab_entry, "max_group": max_group,
+            "eligible": ok}
 
 
 def lambdarank_doc_weight(weights, group_ptr: np.ndarray):
@@ -1746,18 +1790,25 @@ def lambdarank_doc_weight(weights, group_ptr: np.ndarray):
 
 
 class LambdaRankState:
-    """What the ranking kernel needs besides the scores, built once per
+    """What the ranking kernels need besides the scores, built once per
     (MetaInfo, device): device labels and group pointer, the work list of
-    every tier, the per-document weight, 1/IDCG per group (rank:ndcg; it
-    depends on the labels only) and whether the labels are binary
-    (rank:map checks this once here, not every round)."""
+    every tier, the slab tier's items, offsets and scratch sizes for the
+    truncation level `k`, the per-document weight, 1/IDCG per group
+    (rank:ndcg; it depends on the labels only) and whether the labels are
+    binary (rank:map checks this once here, not every round).  `slab`
+    overrides the slab tier's (slab, kernel shape id), for timing the
+    other shapes."""
 
     def __init__(self, labels, group_ptr, weights, device,
-                 inv_idcg: Optional[np.ndarray] = None):
+                 inv_idcg: Optional[np.ndarray] = None,
+                 k: int = LAMBDARANK_DEFAULT_K,
+                 slab: Optional[Tuple[int, int]] = None):
         y = np.ascontiguousarray(np.asarray(labels).reshape(-1), np.float32)
         gp = np.ascontiguousarray(np.asarray(group_ptr).reshape(-1),
                                   np.int64)
-        sched = lambdarank_schedule(gp)
+        self.k = int(k)
+        self.slab_shape = LAMBDARANK_SLAB if slab is None else slab
+        sched = lambdarank_schedule(gp, self.k, self.slab_shape[0])
         self.n = int(y.shape[0])
         self.n_groups = int(gp.size - 1)
         self.max_group = sched["max_group"]
@@ -1769,6 +1820,13 @@ class LambdaRankState:
         self.group_ptr = torch.from_numpy(gp).to(device)
         self.work = {name: torch.from_numpy(ids).to(device)
                      for name, ids in sched["lists"].items() if ids.size}
+        sl = sched["slab"]
+        self.slab = None  # no group above the LDS tiers: no slab launches
+        if sl["items"].shape[0]:
+            self.slab = {name: torch.from_numpy(a).to(device)
+                         for name, a in sl.items()}
+            self.slab_docs = int(sl["doc_off"][-1])
+            self.slab_rows = int(sl["row_off"][-1])
         w = lambdarank_doc_weight(weights, gp)
         self.weight = (None if w is None else
                        torch.from_numpy(np.ascontiguousarray(w)).to(device))
@@ -1780,9 +1838,11 @@ def lambdarank_gpair_gpu(scores: torch.Tensor, state: LambdaRankState,
                          metric: str, k: int, score_norm: bool,
                          normalize: bool, exp_gain: bool
                          ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """LambdaMART (g, h), fp32 [N], for fp32 device scores [N]: one kernel
-    launch per non-empty tier, top-k pair method.  The kernel writes every
-    document, so the outputs are not cleared first."""
+    """LambdaMART (g, h), fp32 [N], for fp32 device scores [N], top-k pair
+    method: one kernel launch per non-empty LDS tier, then the slab
+    tier's three or four launches when a group is above
+    LAMBDARANK_LDS_MAX_GROUP.  Between them the kernels write every
+    document, so the outputs are not cleared first.  No host sync."""
     from .. import ops as hip_ops
     lib = hip_ops.load()
     if not hasattr(lib, "gbt_lambdarank"):
@@ -1791,7 +1851,9 @@ def lambdarank_gpair_gpu(scores: torch.Tensor, state: LambdaRankState,
     if not state.eligible:
         raise ValueError(
             f"ranking kernel: groups of up to {LAMBDARANK_MAX_GROUP} "
-            f"documents covering every row, got {state.max_group}")
+            f"documents covering every row and at most "
+            f"{LAMBDARANK_SLAB_ROWS} slab row shares, got a group of "
+            f"{state.max_group}")
     m = LAMBDARANK_METRICS[metric]
     if metric == "map" and not state.binary_labels:
         raise ValueError("rank:map requires binary labels")
@@ -1811,6 +1873,33 @@ def lambdarank_gpair_gpu(scores: torch.Tensor, state: LambdaRankState,
             int(k), int(bool(score_norm)), int(bool(normalize)),
             int(bool(exp_gain)), hip_ops.ptr(g), hip_ops.ptr(h),
             hip_ops.stream())
+    if state.slab is not None:
+        if not hasattr(lib, "gbt_lambdarank_slab"):
+            raise RuntimeError(
+                "libgbt_hip.so has no gbt_lambdarank_slab; rebuild it "
+                "(xgboost_amd/ops/build_ext.py --force)")
+        if int(k) != state.k:
+            raise ValueError(f"the state's slab scratch is sized for k = "
+                             f"{state.k}, got k = {k}")
+        slab, shape = state.slab_shape
+        assert lib.gbt_lambdarank_slab_size(shape) == slab, (slab, shape)
+        sl, dev = state.slab, scores.device
+        n_items = sl["items"].shape[0]
+        f32 = torch.empty(2 * state.slab_docs, dtype=torch.float32,
+                          device=dev)
+        i32 = torch.empty(state.slab_docs, dtype=torch.int32, device=dev)
+        f64 = torch.empty(4 * state.slab_docs + 2 * state.slab_rows + n_items,
+                          dtype=torch.float64, device=dev)
+        lib.gbt_lambdarank_slab(
+            m, shape, hip_ops.ptr(scores), hip_ops.ptr(state.labels),
+            hip_ops.ptr(state.group_ptr), hip_ops.ptr(state.inv_idcg),
+            hip_ops.ptr(state.weight), hip_ops.ptr(sl["items"]), n_items,
+            hip_ops.ptr(sl["item_off"]), hip_ops.ptr(sl["doc_off"]),
+            hip_ops.ptr(sl["row_off"]), min(state.k, 2 ** 31 - 1),
+            int(bool(score_norm)), int(bool(normalize)), int(bool(exp_gain)),
+            state.slab_docs, state.slab_rows, hip_ops.ptr(f32),
+            hip_ops.ptr(i32), hip_ops.ptr(f64), hip_ops.ptr(g),
+            hip_ops.ptr(h), hip_ops.stream())
     return g, h
 
 

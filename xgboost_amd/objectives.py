@@ -812,7 +812,7 @@ class _LambdaRankBase(Objective):
                 pos = torch.arange(y.numel()) - gp[gid]
                 inv_idcg = self._prepare(y, cnt, gp, pos)["inv_idcg"].numpy()
             state = LambdaRankState(info.labels, gp_np, info.weights,
-                                    preds.device, inv_idcg)
+                                    preds.device, inv_idcg, self._k())
             self_ref = weakref.ref(self)
 
             def _evict(_, self_ref=self_ref):
@@ -826,13 +826,16 @@ class _LambdaRankBase(Objective):
 
     # -- main --------------------------------------------------------------
     def get_gradient(self, preds, info, it):
-        """Device predictions with the top-k pair method run as one HIP
-        kernel launch per group-size tier (ops/cpp/lambdarank.hip).  The
-        torch formulation below serves everything else: CPU tensors, the
-        `mean` pair method (host RNG), unbiased LambdaMART (position state
-        across groups and rounds), a group above the kernel's capacity
-        (backend.gpu.LAMBDARANK_MAX_GROUP documents), a library without
-        the kernel, and XGB_AMD_RANK_HIP=0."""
+        """Device predictions with the top-k pair method run as HIP
+        kernels: one launch per group-size tier for groups of up to 2048
+        documents (ops/cpp/lambdarank.hip) and the slab tier's chain for
+        longer ones (ops/cpp/lambdarank_slab.hip).  The torch formulation
+        below serves everything else: CPU tensors, the `mean` pair method
+        (host RNG), unbiased LambdaMART (position state across groups and
+        rounds), a group above backend.gpu.LAMBDARANK_MAX_GROUP documents,
+        a truncation level that needs more than
+        backend.gpu.LAMBDARANK_SLAB_ROWS slab row shares, a library
+        without the kernel, and XGB_AMD_RANK_HIP=0."""
         state = self._hip_state(preds, info)
         if state is not None:
             from .backend.gpu import lambdarank_gpair_gpu

@@ -67,6 +67,13 @@ _SIGS = {
     "gbt_lambdarank": [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i,
                        _p, _p, _p],
     "gbt_lambdarank_tier_cap": [_i],
+    # metric, shape, scores, labels, group_ptr, inv_idcg, weight, items,
+    # n_items, item_off, doc_off, row_off, k, score_norm, normalize,
+    # exp_gain, n_docs, n_rows, scratch f32 / i32 / f64, out_g, out_h
+    "gbt_lambdarank_slab": [_i, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p,
+                            _i, _i, _i, _i, _i64, _i64, _p, _p, _p, _p, _p,
+                            _p],
+    "gbt_lambdarank_slab_size": [_i],
     # kind, tier, scores, labels, group_ptr, work, n_work, k, part_off,
     # partial
     "gbt_rank_metric": [_i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p],
@@ -164,6 +171,8 @@ def load() -> ctypes.CDLL:
         _lib.gbt_wt_arena_bytes.restype = _c.c_longlong
     if hasattr(_lib, "gbt_lambdarank_tier_cap"):
         _lib.gbt_lambdarank_tier_cap.restype = _c.c_int
+    if hasattr(_lib, "gbt_lambdarank_slab_size"):
+        _lib.gbt_lambdarank_slab_size.restype = _c.c_int
     if hasattr(_lib, "gbt_rank_metric_slab"):
         _lib.gbt_rank_metric_slab.restype = _c.c_int
     if hasattr(_lib, "gbt_shap_saabas_rows"):

@@ -15,7 +15,7 @@ SOURCES = ["hist.hip", "partition.hip", "evaluate.hip", "compress.hip",
            "shap_paths.hip", "shap_ix.hip", "shap_csr.hip",
            "driver.hip", "csr.hip", "gpair.hip", "mt_evaluate.hip",
            "cpu_hist.cpp", "lambdarank.hip", "rank_metric.hip",
-           "shap_saabas.hip"]
+           "shap_saabas.hip", "lambdarank_slab.hip"]
 
 # Sources compiled on their own, with flags the other kernels were not
 # measured under: the ranking and Saabas kernels keep the compiler from
@@ -26,6 +26,7 @@ _RANK_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
                "-Rpass-analysis=kernel-resource-usage"]
 OWN_FLAGS = {
     "lambdarank.hip": _RANK_FLAGS,
+    "lambdarank_slab.hip": _RANK_FLAGS,
     "rank_metric.hip": _RANK_FLAGS,
     "shap_saabas.hip": _RANK_FLAGS,
 }

@@ -205,6 +205,33 @@ void gbt_lambdarank(int metric, int tier, const float* scores,
 // Largest group a tier holds; 0 for an unknown tier.
 int gbt_lambdarank_tier_cap(int tier);
 
+// LambdaMART gradients for groups above the LDS tiers' capacity
+// (lambdarank_slab.hip): rank, [map statistics,] pairs and finish launches
+// over `items`, {group, slab start} pairs with slab starts multiples of
+// gbt_lambdarank_slab_size(shape).  item_off[g] is group g's first item
+// slot, doc_off[g] its first slot in the by-rank scratch arrays and
+// row_off[g] its first row-share entry, items(g) * min(k, n_g) of them.
+// Scratch: 2 * n_docs floats, n_docs ints, 4 * n_docs + 2 * n_rows +
+// n_items doubles; none of it needs clearing.  Writes g and h of every
+// document of the listed groups.
+void gbt_lambdarank_slab(int metric, int shape, const float* scores,
+                         const float* labels,
+                         const long long* group_ptr,  // [G+1]
+                         const double* inv_idcg,      // [G], ndcg only
+                         const double* weight,        // [N] or null
+                         const int32_t* items, int n_items,
+                         const int32_t* item_off,     // [G+1]
+                         const long long* doc_off,    // [G+1]
+                         const long long* row_off,    // [G+1]
+                         int k, int score_norm, int normalize, int exp_gain,
+                         long long n_docs, long long n_rows,
+                         float* scratch_f32, int32_t* scratch_i32,
+                         double* scratch_f64, float* out_g, float* out_h,
+                         hipStream_t stream);
+
+// Documents per work item of a slab shape; 0 for an unknown shape.
+int gbt_lambdarank_slab_size(int shape);
+
 // Ranking metrics by counting (rank_metric.hip), one launch per tier.
 // kind: 0 = ndcg, 1 = map, 2 = pre.  Tier 0 takes `work` as group ids of
 // 1..64 documents; every other tier takes {group, slab start} pairs, slab
