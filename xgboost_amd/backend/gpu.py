@@ -1699,6 +1699,68 @@ def predict_margin_csr_gpu(booster, dmat, out: Optional[torch.Tensor],
 
 
 # ---------------------------------------------------------------------------
+# Multiclass softmax gradients (softmax_gpair.hip) and the batched quantise
+
+# block shape id -> largest K it serves.  The even ids are the defaults of
+# the three K tiers, the odd ids the alternatives timed against them in
+# profiles/multiclass_mi355x.md.
+SOFTMAX_GPAIR_SHAPES = {0: 16, 1: 16, 2: 64, 3: 64, 4: 256, 5: 256}
+
+
+def _softmax_lib():
+    from .. import ops as hip_ops
+    lib = hip_ops.load()
+    if not hasattr(lib, "gbt_softmax_gpair"):
+        raise RuntimeError("libgbt_hip.so has no gbt_softmax_gpair; rebuild "
+                           "it (xgboost_amd/ops/build_ext.py --force)")
+    return hip_ops, lib
+
+
+def softmax_gpair_max_classes() -> int:
+    """Largest class count the softmax gradient kernel serves."""
+    return int(_softmax_lib()[1].gbt_softmax_gpair_max_classes())
+
+
+def softmax_gpair_gpu(margin: torch.Tensor, labels: torch.Tensor,
+                      weights: Optional[torch.Tensor], out_gh: torch.Tensor,
+                      out_maxabs: torch.Tensor, shape: int = -1) -> None:
+    """Softmax (g, h) of fp32 device margins [n, K] into the class-major
+    planes out_gh [K, n, 2] and their max-abs into out_maxabs [K, 2], which
+    the caller has zeroed.  One launch, no host sync.  `shape` picks a block
+    shape of SOFTMAX_GPAIR_SHAPES; the default is the one chosen for K."""
+    hip_ops, lib = _softmax_lib()
+    n, K = margin.shape
+    assert margin.is_cuda and margin.dtype == torch.float32
+    assert labels.dtype == torch.float32 and labels.numel() == n
+    assert weights is None or (weights.dtype == torch.float32
+                               and weights.numel() == n)
+    assert out_gh.dtype == torch.float32 and out_gh.shape == (K, n, 2)
+    assert out_maxabs.dtype == torch.float32 and out_maxabs.shape == (K, 2)
+    rc = lib.gbt_softmax_gpair_shaped(
+        int(shape), hip_ops.ptr(margin), hip_ops.ptr(labels),
+        hip_ops.ptr(weights), n, K, hip_ops.ptr(out_gh),
+        hip_ops.ptr(out_maxabs), hip_ops.stream())
+    if rc != 0:
+        raise ValueError(f"softmax gradient kernel: shape {shape} does not "
+                         f"serve {K} classes")
+
+
+def quantize_planes_gpu(gh: torch.Tensor, maxabs: torch.Tensor,
+                        out: torch.Tensor, out_sums: torch.Tensor) -> None:
+    """Fixed-point quantise of the planes gh [K, n, 2] into out (int32, same
+    shape), plane k scaled by 2^30 / maxabs[k]; out_sums [K, 2] (int64,
+    zeroed by the caller) receives each plane's exact totals."""
+    hip_ops, lib = _softmax_lib()
+    K, n, _ = gh.shape
+    assert gh.dtype == torch.float32 and out.dtype == torch.int32
+    assert out.shape == gh.shape and maxabs.shape == (K, 2)
+    assert out_sums.dtype == torch.int64 and out_sums.shape == (K, 2)
+    lib.gbt_quantize_planes(hip_ops.ptr(gh), n, K, hip_ops.ptr(maxabs),
+                            hip_ops.ptr(out), hip_ops.ptr(out_sums),
+                            hip_ops.stream())
+
+
+# ---------------------------------------------------------------------------
 # LambdaMART gradients (lambdarank.hip, lambdarank_slab.hip)
 
 # The largest group the kernel path takes.  The slab tier ranks by counting,

@@ -509,7 +509,14 @@ class Booster:
             return False
         obj_id = {"binary:logistic": 0, "reg:squarederror": 1}.get(
             self.objective.name)
-        if obj_id is None or self.n_outputs != 1:
+        multi = self.objective.name in ("multi:softmax", "multi:softprob")
+        if multi:
+            # XGB_AMD_FUSED_MULTI=0 keeps multiclass on the generic chain
+            if (os.environ.get("XGB_AMD_FUSED_MULTI", "1") == "0"
+                    or self.n_outputs != self.objective.num_class
+                    or self._dart_track()):
+                return False
+        elif obj_id is None or self.n_outputs != 1:
             return False
         tp = self.tparam
         if (tp.subsample < 1.0 or tp.num_parallel_tree != 1
@@ -525,6 +532,8 @@ class Booster:
             lib = hip_ops.load()
         except RuntimeError:
             return False
+        if multi:
+            return self._boost_fused_multi(dtrain, margin, iteration, lib)
         if not hasattr(lib, "gbt_gpair_fused"):
             return False
         ops = self._ops_for(dtrain)
@@ -597,6 +606,96 @@ class Booster:
         else:
             leaf_vals = torch.as_tensor(leaf_np, device=margin.device)
             margin[:, 0] += leaf_vals[positions.to(margin.device).long()]
+        self._cache[key] = (margin, len(self.trees))
+        if self.tparam.debug_synchronize:
+            collective.check_synchronized(
+                json.dumps(self.trees[-1].to_json()).encode(), "tree")
+        return True
+
+    def _boost_fused_multi(self, dtrain: DMatrix, margin: torch.Tensor,
+                           iteration: int, lib) -> bool:
+        """The fused round for multi:softmax / multi:softprob: one softmax
+        gradient launch writes a (g, h) plane and its max-abs per class
+        (ops/cpp/softmax_gpair.hip), one launch quantises all planes, then
+        the classes' trees grow in order, each consuming its plane as the
+        binary path consumes its [n, 2] pairs.  All K gradients come from
+        the margin as it stands before the round's first tree, as on the
+        generic path.  Returns False (generic path) when the library lacks
+        the kernels, K is above their cap, the margin is not a contiguous
+        fp32 [n, K] or a label is not a class index."""
+        K = self.n_outputs
+        n = dtrain.num_row()
+        if not (hasattr(lib, "gbt_softmax_gpair")
+                and hasattr(lib, "gbt_quantize_planes")
+                and hasattr(lib, "gbt_margin_add")):
+            return False
+        if K > lib.gbt_softmax_gpair_max_classes() or n == 0:
+            return False
+        if not (margin.dtype == torch.float32 and margin.is_contiguous()
+                and margin.shape == (n, K)):
+            return False
+        ops = self._ops_for(dtrain)
+        if not hasattr(ops, "stager"):
+            return False
+        from . import ops as hip_ops
+        from .backend.gpu import quantize_planes_gpu, softmax_gpair_gpu
+        key = self._pin(dtrain)
+        ent = self.__dict__.get("_fused_cache", {}).get(key)
+        if ent is None:
+            y = np.ascontiguousarray(dtrain.get_label(), np.float32).ravel()
+            if y.size != n or not bool(np.all((y > -1.0) & (y < K))):
+                # what the generic path makes of such labels stays its call
+                return False
+            dev = self.device
+            w = dtrain.info.weights
+            ent = {"labels": torch.as_tensor(y, device=dev),
+                   "weights": (torch.as_tensor(
+                       np.ascontiguousarray(w, np.float32), device=dev)
+                       if w is not None else None),
+                   "gh": torch.empty((K, n, 2), dtype=torch.float32,
+                                     device=dev),
+                   "qg": torch.empty((K, n, 2), dtype=torch.int32,
+                                     device=dev),
+                   "maxabs": torch.zeros((K, 2), dtype=torch.float32,
+                                         device=dev),
+                   "rootsum": torch.zeros((K, 2), dtype=torch.int64,
+                                          device=dev)}
+            self.__dict__.setdefault("_fused_cache", {})[key] = ent
+        m, rs = ent["maxabs"], ent["rootsum"]
+        m.zero_()
+        rs.zero_()
+        softmax_gpair_gpu(margin, ent["labels"], ent["weights"], ent["gh"], m)
+        if collective.is_distributed():
+            collective.allreduce_max_(m)
+        quantize_planes_gpu(ent["gh"], m, ent["qg"], rs)
+        if collective.is_distributed():
+            collective.allreduce_sum_(rs)
+        seed = (self.seed + iteration if not self.seed_per_iteration
+                else self.seed + iteration * 2654435761)
+        tp = self.tparam
+        for k in range(K):
+            # scales stay on the device, as in _boost_fused
+            quantizer = GradQuantizer.__new__(GradQuantizer)
+            quantizer.g_scale = None
+            quantizer.h_scale = None
+            quantizer.maxabs_dev = m[k]
+            quantizer.root_sums_dev = rs[k]
+            grower = TreeGrower(ops, tp, quantizer, n, seed=seed + 17 * k,
+                                monotone=self._monotone_array(),
+                                interaction=tp.interaction_constraints,
+                                feature_weights=dtrain.info.feature_weights)
+            tree, positions = grower.grow(ent["qg"][k],
+                                          RegTree(self.n_features))
+            self.trees.append(tree)
+            self.tree_info.append(k)
+            (leaf_vals,) = ops.stager.upload(
+                [tree.split_cond[:tree.n_nodes].copy()])
+            lib.gbt_margin_add(
+                hip_ops.ptr(margin),
+                hip_ops.ptr(positions.to(device=margin.device,
+                                         dtype=torch.int32).contiguous()),
+                hip_ops.ptr(leaf_vals), n, K, k, hip_ops.stream())
+        self.iteration_indptr.append(self.iteration_indptr[-1] + K)
         self._cache[key] = (margin, len(self.trees))
         if self.tparam.debug_synchronize:
             collective.check_synchronized(

@@ -62,6 +62,13 @@ _SIGS = {
     "gbt_gpair_fused": [_i, _p, _p, _p, _f, _i64, _p, _p, _p],
     "gbt_quantize": [_p, _i64, _d, _d, _p, _p, _p, _p],
     "gbt_margin_add": [_p, _p, _p, _i64, _i, _i, _p],
+    # margin [n, K], label, weight, n, K, out_gh [K][n][2], out_maxabs
+    # [K][2]; _shaped takes the block shape id first
+    "gbt_softmax_gpair": [_p, _p, _p, _i64, _i, _p, _p, _p],
+    "gbt_softmax_gpair_shaped": [_i, _p, _p, _p, _i64, _i, _p, _p, _p],
+    "gbt_softmax_gpair_max_classes": [],
+    # gh [K][n][2], n, K, maxabs [K][2], out, out_sums [K][2]
+    "gbt_quantize_planes": [_p, _i64, _i, _p, _p, _p, _p],
     # metric, tier, scores, labels, group_ptr, inv_idcg, weight, work,
     # n_work, k, score_norm, normalize, exp_gain, out_g, out_h
     "gbt_lambdarank": [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i,
@@ -171,6 +178,10 @@ def load() -> ctypes.CDLL:
         _lib.gbt_wt_arena_bytes.restype = _c.c_longlong
     if hasattr(_lib, "gbt_lambdarank_tier_cap"):
         _lib.gbt_lambdarank_tier_cap.restype = _c.c_int
+    for name in ("gbt_softmax_gpair", "gbt_softmax_gpair_shaped",
+                 "gbt_softmax_gpair_max_classes"):
+        if hasattr(_lib, name):
+            getattr(_lib, name).restype = _c.c_int
     if hasattr(_lib, "gbt_lambdarank_slab_size"):
         _lib.gbt_lambdarank_slab_size.restype = _c.c_int
     if hasattr(_lib, "gbt_rank_metric_slab"):

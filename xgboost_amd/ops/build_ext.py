@@ -15,13 +15,14 @@ SOURCES = ["hist.hip", "partition.hip", "evaluate.hip", "compress.hip",
            "shap_paths.hip", "shap_ix.hip", "shap_csr.hip",
            "driver.hip", "csr.hip", "gpair.hip", "mt_evaluate.hip",
            "cpu_hist.cpp", "lambdarank.hip", "rank_metric.hip",
-           "shap_saabas.hip", "lambdarank_slab.hip"]
+           "shap_saabas.hip", "lambdarank_slab.hip", "softmax_gpair.hip"]
 
 # Sources compiled on their own, with flags the other kernels were not
-# measured under: the ranking and Saabas kernels keep the compiler from
-# pairing fp32 operations into packed instructions and print the per-kernel
-# resource usage (registers, LDS, scratch, occupancy;
-# profiles/lambdarank_mi355x.md, profiles/shap_approx_mi355x.md).
+# measured under: the ranking, Saabas and softmax-gradient kernels keep the
+# compiler from pairing fp32 operations into packed instructions and print
+# the per-kernel resource usage (registers, LDS, scratch, occupancy;
+# profiles/lambdarank_mi355x.md, profiles/shap_approx_mi355x.md,
+# profiles/multiclass_mi355x.md).
 _RANK_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
                "-Rpass-analysis=kernel-resource-usage"]
 OWN_FLAGS = {
@@ -29,6 +30,9 @@ OWN_FLAGS = {
     "lambdarank_slab.hip": _RANK_FLAGS,
     "rank_metric.hip": _RANK_FLAGS,
     "shap_saabas.hip": _RANK_FLAGS,
+    "softmax_gpair.hip": _RANK_FLAGS,
+    # holds the batched quantise kernel that follows softmax_gpair.hip
+    "gpair.hip": _RANK_FLAGS,
 }
 
 

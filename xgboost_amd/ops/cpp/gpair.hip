@@ -75,7 +75,9 @@ __global__ __launch_bounds__(256) void GpairKernel(
   }
 }
 
-__global__ __launch_bounds__(256) void QuantizeKernel(
+// One [n, 2] plane, strided over by the blocks of grid dimension x: the
+// body of both quantise kernels below.
+__device__ inline void QuantizePlane(
     const float* __restrict__ gh, long long n, double g_scale, double h_scale,
     const float* __restrict__ maxabs /* null, or [2]: derive the scales
         here so the host never has to read max-abs back */,
@@ -125,6 +127,25 @@ __global__ __launch_bounds__(256) void QuantizeKernel(
   }
 }
 
+__global__ __launch_bounds__(256) void QuantizeKernel(
+    const float* __restrict__ gh, long long n, double g_scale, double h_scale,
+    const float* __restrict__ maxabs, int32_t* __restrict__ out,
+    int64_t* __restrict__ out_sums) {
+  QuantizePlane(gh, n, g_scale, h_scale, maxabs, out, out_sums);
+}
+
+// K planes in one launch, blockIdx.y the plane: plane k scales by its own
+// maxabs[k] and accumulates its own out_sums[k].
+__global__ __launch_bounds__(256) void QuantizePlanesKernel(
+    const float* __restrict__ gh /* [K][n][2] */, long long n,
+    const float* __restrict__ maxabs /* [K][2] */,
+    int32_t* __restrict__ out /* [K][n][2] */,
+    int64_t* __restrict__ out_sums /* [K][2] zero-initialized */) {
+  const long long k = blockIdx.y;
+  QuantizePlane(gh + 2 * k * n, n, 0.0, 0.0, maxabs + 2 * k,
+                out + 2 * k * n, out_sums + 2 * k);
+}
+
 }  // namespace
 
 extern "C" {
@@ -155,6 +176,20 @@ void gbt_quantize(const float* gh, long long n, double g_scale,
   const int blocks = (int)std::min<long long>((n + 255) / 256, 512);
   hipLaunchKernelGGL(QuantizeKernel, dim3(blocks), dim3(256), 0, stream, gh,
                      n, g_scale, h_scale, maxabs, out, out_sums);
+}
+
+// gbt_quantize over K class-major planes (softmax_gpair.hip's output) with
+// device-side scales: same rounding, scale formula and exact int64 sums.
+void gbt_quantize_planes(const float* gh, long long n, int n_planes,
+                         const float* maxabs, int32_t* out, int64_t* out_sums,
+                         hipStream_t stream) {
+  if (n <= 0 || n_planes <= 0) return;
+  // the per-plane atomic tail is gbt_quantize's; the grid as a whole is
+  // kept near its size
+  const int per = std::max(512 / n_planes, 64);
+  const int blocks = (int)std::min<long long>((n + 255) / 256, per);
+  hipLaunchKernelGGL(QuantizePlanesKernel, dim3(blocks, n_planes), dim3(256),
+                     0, stream, gh, n, maxabs, out, out_sums);
 }
 
 }  // extern "C"
