@@ -1761,6 +1761,65 @@ def quantize_planes_gpu(gh: torch.Tensor, maxabs: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# Gradient-based row sampling (mvs_sample.hip)
+
+# (device index, stream) -> the kernel's scratch tables.  Zeroed once here;
+# every call leaves them zeroed again.
+_MVS_SCRATCH: dict = {}
+
+
+def mvs_sample_available() -> bool:
+    """True when the library is loadable and has the sampling kernel."""
+    from .. import ops as hip_ops
+    return hip_ops.available() and hasattr(hip_ops.load(), "gbt_mvs_sample")
+
+
+def mvs_sample_gpu(gh: torch.Tensor, subsample: float, reg_lambda: float,
+                   seed: int, out: Optional[torch.Tensor] = None,
+                   maxabs: Optional[torch.Tensor] = None,
+                   rand: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """sampling_method=gradient_based on fp32 device pairs gh [n, 2]: keeps
+    row i with probability kp_i = min(1, s_i / u), s_i = sqrt(g_i^2 +
+    reg_lambda * h_i^2), where u makes the kp_i sum to subsample * n over
+    these rows, and scales a kept row by 1 / kp_i.  Returns (out, u): `out`
+    (default: a new tensor; may be gh itself) holds the sampled pairs, u is
+    a device fp64 scalar (0 when no more than subsample * n rows have a
+    positive score; those are then all kept unscaled).  `maxabs` [2], zeroed
+    by the caller, receives the max |g|, |h| written.  The draws come from
+    Philox4x32-10 on (seed, row), or from `rand` [n] when given.  Four
+    launches, no host sync."""
+    from .. import ops as hip_ops
+    lib = hip_ops.load()
+    if not hasattr(lib, "gbt_mvs_sample"):
+        raise RuntimeError("libgbt_hip.so has no gbt_mvs_sample; rebuild it "
+                           "(xgboost_amd/ops/build_ext.py --force)")
+    assert gh.is_cuda and gh.dtype == torch.float32
+    assert gh.dim() == 2 and gh.shape[1] == 2
+    n = gh.shape[0]
+    if out is None:
+        out = torch.empty_like(gh)
+    assert out.dtype == torch.float32 and out.shape == gh.shape
+    assert maxabs is None or (maxabs.dtype == torch.float32
+                              and maxabs.numel() == 2)
+    assert rand is None or (rand.dtype == torch.float32
+                            and rand.numel() == n)
+    key = (gh.device.index, torch.cuda.current_stream(gh.device).cuda_stream)
+    tables = _MVS_SCRATCH.get(key)
+    if tables is None:
+        words = int(lib.gbt_mvs_sample_scratch_bytes()) // 8
+        tables = torch.zeros(words, dtype=torch.int64, device=gh.device)
+        _MVS_SCRATCH[key] = tables
+    threshold = torch.zeros((), dtype=torch.float64, device=gh.device)
+    lib.gbt_mvs_sample(hip_ops.ptr(gh), n, float(reg_lambda),
+                       float(subsample) * n, int(seed) & (2 ** 64 - 1),
+                       hip_ops.ptr(rand), hip_ops.ptr(tables),
+                       hip_ops.ptr(out), hip_ops.ptr(maxabs),
+                       hip_ops.ptr(threshold), hip_ops.stream())
+    return out, threshold
+
+
+# ---------------------------------------------------------------------------
 # LambdaMART gradients (lambdarank.hip, lambdarank_slab.hip)
 
 # The largest group the kernel path takes.  The slab tier ranks by counting,

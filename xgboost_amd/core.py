@@ -519,7 +519,13 @@ class Booster:
         elif obj_id is None or self.n_outputs != 1:
             return False
         tp = self.tparam
-        if (tp.subsample < 1.0 or tp.num_parallel_tree != 1
+        # sampling stays fused only as gradient-based sampling of a single
+        # output, done in place by the device kernel (ops/cpp/mvs_sample.hip)
+        mvs = tp.subsample < 1.0
+        if mvs and (multi or tp.sampling_method != "gradient_based"
+                    or not _mvs_hip()):
+            return False
+        if (tp.num_parallel_tree != 1
                 or tp.tree_method not in ("auto", "hist")
                 or self.booster_kind == "gblinear"
                 or tp.process_type == "update"
@@ -562,6 +568,15 @@ class Booster:
             spw, n, hip_ops.ptr(ent["gh"]), hip_ops.ptr(ent["maxabs"]),
             hip_ops.stream())
         m = ent["maxabs"]
+        seed = (self.seed + iteration if not self.seed_per_iteration
+                else self.seed + iteration * 2654435761)
+        if mvs:
+            # sampling rescales the kept rows: the max-abs of the unsampled
+            # pairs is discarded and taken again from what is written
+            from .backend.gpu import mvs_sample_gpu
+            m.zero_()
+            mvs_sample_gpu(ent["gh"], tp.subsample, tp.reg_lambda, seed,
+                           out=ent["gh"], maxabs=m)
         if collective.is_distributed():
             collective.allreduce_max_(m)
         # scales are derived ON DEVICE (QuantizeKernel / root eval) and
@@ -582,8 +597,6 @@ class Booster:
         if collective.is_distributed():
             collective.allreduce_sum_(ent["rootsum"])
         quantizer.root_sums_dev = ent["rootsum"]
-        seed = (self.seed + iteration if not self.seed_per_iteration
-                else self.seed + iteration * 2654435761)
         tree = RegTree(self.n_features)
         grower = TreeGrower(ops, self.tparam, quantizer, n, seed=seed,
                             monotone=self._monotone_array(),
@@ -952,6 +965,12 @@ class Booster:
         p = self.tparam.subsample
         if p >= 1.0:
             return gpair
+        if (self.tparam.sampling_method == "gradient_based" and gpair.is_cuda
+                and gpair.dtype == torch.float32 and _mvs_hip()):
+            # threshold, draws and scaling on the device, no host round trip
+            from .backend.gpu import mvs_sample_gpu
+            return mvs_sample_gpu(gpair.contiguous(), p,
+                                  self.tparam.reg_lambda, seed)[0]
         gen = torch.Generator(device="cpu").manual_seed(seed & 0x7FFFFFFF)
         if self.tparam.sampling_method == "gradient_based":
             # MVS-style: keep prob proportional to sqrt(g^2 + lambda*h^2)
@@ -1699,6 +1718,15 @@ def _parse_model_bytes(data: bytes, force_ubj: bool) -> dict:
             pass
     from .ubjson import loads_ubjson
     return loads_ubjson(data)
+
+
+def _mvs_hip() -> bool:
+    """Whether gradient-based sampling of device gradients runs in the HIP
+    kernel (ops/cpp/mvs_sample.hip).  XGB_AMD_MVS_HIP=0 keeps the host path."""
+    if os.environ.get("XGB_AMD_MVS_HIP", "1") == "0":
+        return False
+    from .backend.gpu import mvs_sample_available
+    return mvs_sample_available()
 
 
 def _sample_rate_threshold(score: torch.Tensor, p: float) -> float:

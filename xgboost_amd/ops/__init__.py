@@ -69,6 +69,11 @@ _SIGS = {
     "gbt_softmax_gpair_max_classes": [],
     # gh [K][n][2], n, K, maxabs [K][2], out, out_sums [K][2]
     "gbt_quantize_planes": [_p, _i64, _i, _p, _p, _p, _p],
+    # gh [n, 2], n, reg_lambda, target_rows, seed, rand | null, tables,
+    # out_gh, out_maxabs | null, out_threshold
+    "gbt_mvs_sample": [_p, _i64, _f, _d, _c.c_uint64, _p, _p, _p, _p, _p,
+                       _p],
+    "gbt_mvs_sample_scratch_bytes": [],
     # metric, tier, scores, labels, group_ptr, inv_idcg, weight, work,
     # n_work, k, score_norm, normalize, exp_gain, out_g, out_h
     "gbt_lambdarank": [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i,
@@ -182,6 +187,8 @@ def load() -> ctypes.CDLL:
                  "gbt_softmax_gpair_max_classes"):
         if hasattr(_lib, name):
             getattr(_lib, name).restype = _c.c_int
+    if hasattr(_lib, "gbt_mvs_sample_scratch_bytes"):
+        _lib.gbt_mvs_sample_scratch_bytes.restype = _c.c_size_t
     if hasattr(_lib, "gbt_lambdarank_slab_size"):
         _lib.gbt_lambdarank_slab_size.restype = _c.c_int
     if hasattr(_lib, "gbt_rank_metric_slab"):

@@ -15,7 +15,8 @@ SOURCES = ["hist.hip", "partition.hip", "evaluate.hip", "compress.hip",
            "shap_paths.hip", "shap_ix.hip", "shap_csr.hip",
            "driver.hip", "csr.hip", "gpair.hip", "mt_evaluate.hip",
            "cpu_hist.cpp", "lambdarank.hip", "rank_metric.hip",
-           "shap_saabas.hip", "lambdarank_slab.hip", "softmax_gpair.hip"]
+           "shap_saabas.hip", "lambdarank_slab.hip", "softmax_gpair.hip",
+           "mvs_sample.hip"]
 
 # Sources compiled on their own, with flags the other kernels were not
 # measured under: the ranking, Saabas and softmax-gradient kernels keep the
@@ -33,6 +34,9 @@ OWN_FLAGS = {
     "softmax_gpair.hip": _RANK_FLAGS,
     # holds the batched quantise kernel that follows softmax_gpair.hip
     "gpair.hip": _RANK_FLAGS,
+    # its exact scores also need -ffp-contract=off and the default,
+    # correctly rounded sqrtf and division: both hold in `common` below
+    "mvs_sample.hip": _RANK_FLAGS,
 }
 
 

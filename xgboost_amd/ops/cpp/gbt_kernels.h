@@ -283,6 +283,24 @@ void gbt_shap_saabas(const float* X, int64_t n_rows, int64_t row_stride,
 // Rows of one block's tile in gbt_shap_saabas.
 int gbt_shap_saabas_rows();
 
+// Gradient-based (MVS) row sampling (mvs_sample.hip).  Finds the threshold u
+// with sum_i min(1, s_i / u) = target_rows over the scores s_i =
+// sqrtf(g_i^2 + reg_lambda * h_i^2) of gh [n, 2], keeps row i when r_i <
+// kp_i = min(1, s_i / u), writes (g, h) / kp_i for a kept row and (0, 0)
+// for a dropped one to out_gh (which may be gh), u to out_threshold (0 when
+// at most target_rows rows have a positive score: those are all kept
+// unscaled) and, unless null, the max-abs of the written values into the
+// caller-zeroed out_maxabs [2].  r_i is rand[i], or with rand null a
+// Philox4x32-10 draw from (seed, i).  `tables` is
+// gbt_mvs_sample_scratch_bytes() of scratch that the caller zeroes once,
+// before its first use; every call leaves it zeroed for the next.
+void gbt_mvs_sample(const float* gh, long long n, float reg_lambda,
+                    double target_rows, unsigned long long seed,
+                    const float* rand, unsigned long long* tables,
+                    float* out_gh, float* out_maxabs, double* out_threshold,
+                    hipStream_t stream);
+size_t gbt_mvs_sample_scratch_bytes();
+
 void gbt_select_best(const double* gain, const int32_t* bins,
                      const uint8_t* dirs, const int64_t* lsum, int n_nodes,
                      int n_features, int64_t* out_best,
