@@ -339,22 +339,30 @@ class GpuOps(SegmentedOpsMixin):
                      if node_bounds is not None else None)
         mask_np = feature_set_mask(feature_sets, k, f)
         # wide categorical features (cardinality > max_cat_to_onehot) use
-        # sorted-partition splits, evaluated HOST-side with the SAME
-        # routine as the CPU oracle (splits._sorted_cat_split) so GPU and
-        # CPU trees stay identical; mask them out of the kernel's
-        # one-hot/numeric scan
-        wide_feats = None
+        # sorted-partition splits: gbt_evaluate_cat (evaluate_cat.hip) for
+        # the ones up to its width cap, the host routine for wider ones;
+        # both give the CPU oracle's (splits._sorted_cat_split) result, so
+        # GPU and CPU trees stay identical.  All of them are masked out of
+        # the kernel's one-hot/numeric scan
+        wide_feats = kern_feats = None
+        sets_np = None  # the feature sets before the wide columns leave
         if cat_mask is not None:
             widths = np.diff(self.qm.cuts.ptrs)
             wm = np.asarray(cat_mask, bool) & (
                 widths > param.max_cat_to_onehot)
             if wm.any():
                 wide_feats = np.nonzero(wm)[0]
+                served = widths[wide_feats] <= self._cat_hip_cap()
+                if served.any():
+                    kern_feats = wide_feats[served].astype(np.int32)
+                    wide_feats = wide_feats[~served]
+                    sets_np = None if mask_np is None else mask_np.copy()
                 if mask_np is None:
                     mask_np = np.ones((k, f), dtype=np.uint8)
-                mask_np[:, wide_feats] = 0
-        parents, mono_t, bounds_t, mask_t = self.stager.upload(
-            [parents_np, mono_np, bounds_np, mask_np])
+                mask_np[:, wm] = 0
+        parents, mono_t, bounds_t, mask_t, sets_t, kern_t = \
+            self.stager.upload([parents_np, mono_np, bounds_np, mask_np,
+                                sets_np, kern_feats])
         self.lib.gbt_evaluate_masked(
             self.hip.ptr(hist), k, self.n_bins, f,
             self.hip.ptr(self.cut_ptrs), self.hip.ptr(parents), None,
@@ -374,7 +382,34 @@ class GpuOps(SegmentedOpsMixin):
             self.hip.ptr(gain), self.hip.ptr(bins), self.hip.ptr(dirs),
             self.hip.ptr(lsum), k, f, self.hip.ptr(out_best), None,
             self.hip.stream())
+        best_bits = None
+        if kern_feats is not None:
+            # per (node, wide feature) slots, then the strict-'>' merge
+            # into out_best: one more launch chain, one more D2H copy
+            kw = widths[kern_feats]
+            nk = len(kern_feats)
+            words = (int(kw.max()) + 31) // 32
+            slot_rec = torch.empty((k, nk, 4), dtype=torch.int64, device=dev)
+            slot_bits = torch.empty((k, nk, words), dtype=torch.int32,
+                                    device=dev)
+            best_bits_t = torch.empty((k, words), dtype=torch.int32,
+                                      device=dev)
+            self.lib.gbt_evaluate_cat(
+                self.hip.ptr(hist), k, self.n_bins, f,
+                self.hip.ptr(self.cut_ptrs), self.hip.ptr(parents),
+                quantizer.g_scale, quantizer.h_scale,
+                param.reg_lambda, param.reg_alpha, param.max_delta_step,
+                param.min_child_weight,
+                int(min(max(param.max_cat_threshold, 0), 1 << 30)),
+                self.hip.ptr(kern_t), nk,
+                (1 if (kw <= 64).any() else 0) | (2 if (kw > 64).any() else 0),
+                self.hip.ptr(sets_t), self.hip.ptr(slot_rec),
+                self.hip.ptr(slot_bits), words, self.hip.ptr(out_best),
+                self.hip.ptr(best_bits_t), self.hip.stream())
         host = out_best.cpu().numpy()
+        if kern_feats is not None:
+            best_bits = best_bits_t.cpu().numpy()
+            kern_set = frozenset(int(x) for x in kern_feats)
         sel_gain = host[:, 0].view(np.float64)
         sel_bin = host[:, 1]
         sel_dir = host[:, 2]
@@ -396,24 +431,46 @@ class GpuOps(SegmentedOpsMixin):
                 e.right_gq = int(parent_sums[i][0]) - e.left_gq
                 e.right_hq = int(parent_sums[i][1]) - e.left_hq
                 e.is_cat = bool(cat_mask is not None and cat_mask[fidx])
-                if e.is_cat:
+                if best_bits is not None and fidx in kern_set:
+                    # go-RIGHT bitset -> sorted local category ids
+                    w = int(cuts.ptrs[fidx + 1] - cuts.ptrs[fidx])
+                    row = np.unpackbits(best_bits[i].view(np.uint8),
+                                        bitorder="little")[:w]
+                    e.cat_bits = np.nonzero(row)[0].astype(np.int32)
+                elif e.is_cat:
                     e.cat_bits = np.array(
                         [e.split_bin - int(cuts.ptrs[fidx])], dtype=np.int32)
             out.append(e)
-        if wide_feats is not None:
+        if wide_feats is not None and len(wide_feats):
             self._host_sorted_cat(out, hist, parents_np, quantizer, param,
-                                  wide_feats, feature_sets)
+                                  wide_feats, feature_sets,
+                                  kern_set if best_bits is not None
+                                  else frozenset())
         return out
 
+    def _cat_hip_cap(self) -> int:
+        """Widest categorical feature gbt_evaluate_cat serves; 0 with
+        XGB_AMD_CAT_HIP=0 or a library built without it (then every wide
+        feature takes the host routine)."""
+        import os
+        if (os.environ.get("XGB_AMD_CAT_HIP", "1") == "0"
+                or not hasattr(self.lib, "gbt_evaluate_cat")):
+            return 0
+        return int(self.lib.gbt_evaluate_cat_max_width())
+
     def _host_sorted_cat(self, out, hist, parents_np, quantizer, param,
-                         wide_feats, feature_sets) -> None:
+                         wide_feats, feature_sets,
+                         kern_feats=frozenset()) -> None:
         """Sorted-partition categorical splits (reference
         gpu_hist/evaluate_splits.cuh SortHistogram): the per-category
         ratio sort, present-compaction and prefix cumsums run ON DEVICE;
         only the small (k x width) cumsum/order tables come to the host,
         where the final gain math is the SAME numpy ops as the CPU
         oracle (splits._sorted_cat_split), batched over nodes — so GPU
-        and CPU trees stay identical."""
+        and CPU trees stay identical.  kern_feats: the wide features
+        gbt_evaluate_cat has already merged into `out`; on equal gain the
+        lower feature id keeps the split, as if all wide features had been
+        visited in ascending order."""
         from ..splits import calc_gain_given_weight, calc_weight
         cuts = self.qm.cuts
         k = len(out)
@@ -486,7 +543,8 @@ class GpuOps(SegmentedOpsMixin):
                         continue
                     j = int(np.argmax(row))
                     gv = float(row[j])
-                    if gv > e.gain:
+                    if gv > e.gain or (gv == e.gain and int(fi) < e.feature
+                                       and e.feature in kern_feats):
                         e.gain = gv
                         e.feature = int(fi)
                         e.split_bin = b0

@@ -57,6 +57,13 @@ _SIGS = {
                         _p, _p, _p, _p],
     "gbt_copy_ranges": [_p, _p, _p, _i, _p],
     "gbt_select_best": [_p, _p, _p, _p, _i, _i, _p, _p, _p],
+    # hist, k, n_bins, n_features, cut_ptrs, parents, scales (2), lambda,
+    # alpha, max_delta_step, min_child_weight, max_cat_threshold, wide ids,
+    # n_wide, tiers, feature mask | null, slot records, slot bitsets, words,
+    # out_best, out_bits
+    "gbt_evaluate_cat": [_p, _i, _i, _i, _p, _p, _d, _d, _d, _d, _d, _d, _i,
+                         _p, _i, _i, _p, _p, _p, _i, _p, _p, _p],
+    "gbt_evaluate_cat_max_width": [],
     "gbt_mt_evaluate": [_p, _i, _i, _i, _i, _p, _p, _p, _p,
                         _d, _d, _d, _d, _p, _p, _p, _p, _p],
     "gbt_gpair_fused": [_i, _p, _p, _p, _f, _i64, _p, _p, _p],
@@ -187,6 +194,8 @@ def load() -> ctypes.CDLL:
                  "gbt_softmax_gpair_max_classes"):
         if hasattr(_lib, name):
             getattr(_lib, name).restype = _c.c_int
+    if hasattr(_lib, "gbt_evaluate_cat_max_width"):
+        _lib.gbt_evaluate_cat_max_width.restype = _c.c_int
     if hasattr(_lib, "gbt_mvs_sample_scratch_bytes"):
         _lib.gbt_mvs_sample_scratch_bytes.restype = _c.c_size_t
     if hasattr(_lib, "gbt_lambdarank_slab_size"):

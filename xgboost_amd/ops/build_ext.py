@@ -16,7 +16,7 @@ SOURCES = ["hist.hip", "partition.hip", "evaluate.hip", "compress.hip",
            "driver.hip", "csr.hip", "gpair.hip", "mt_evaluate.hip",
            "cpu_hist.cpp", "lambdarank.hip", "rank_metric.hip",
            "shap_saabas.hip", "lambdarank_slab.hip", "softmax_gpair.hip",
-           "mvs_sample.hip"]
+           "mvs_sample.hip", "evaluate_cat.hip"]
 
 # Sources compiled on their own, with flags the other kernels were not
 # measured under: the ranking, Saabas and softmax-gradient kernels keep the
@@ -37,6 +37,9 @@ OWN_FLAGS = {
     # its exact scores also need -ffp-contract=off and the default,
     # correctly rounded sqrtf and division: both hold in `common` below
     "mvs_sample.hip": _RANK_FLAGS,
+    # fp64 and int64 only: just the resource report
+    # (profiles/categorical_mi355x.md)
+    "evaluate_cat.hip": ["-Rpass-analysis=kernel-resource-usage"],
 }
 
 

@@ -306,4 +306,16 @@ void gbt_select_best(const double* gain, const int32_t* bins,
                      int n_features, int64_t* out_best,
                      const int32_t* k_dev, hipStream_t stream);
 
+// Sorted-partition splits of the listed wide categorical features, merged
+// into gbt_select_best's out_best (evaluate_cat.hip).
+int gbt_evaluate_cat_max_width();
+void gbt_evaluate_cat(
+    const int64_t* hist, int n_nodes, int n_bins, int n_features,
+    const int32_t* cut_ptrs, const int64_t* parent_sums, double g_scale,
+    double h_scale, double reg_lambda, double reg_alpha,
+    double max_delta_step, double min_child_weight, int max_cat_threshold,
+    const int32_t* wide, int n_wide, int tiers, const uint8_t* feature_mask,
+    int64_t* slot_rec, uint32_t* slot_bits, int words, int64_t* out_best,
+    uint32_t* out_bits, hipStream_t stream);
+
 }  // extern "C"

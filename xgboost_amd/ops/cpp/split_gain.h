@@ -50,8 +50,16 @@ GBT_HD double CalcWeight(double g, double h, const SplitParams& p) {
   return w;
 }
 
+// kSeq: the regulariser term multiplied left to right, ((h + lam) * w) * w,
+// the order numpy gives splits.calc_gain_given_weight.  The two orders can
+// differ in the last bit.  The sorted-partition categorical kernel
+// (evaluate_cat.hip) takes kSeq so that its gains equal, bit for bit, the
+// host routine it replaces (splits._sorted_cat_split); every other
+// evaluator keeps the default.
+template <bool kSeq = false>
 GBT_HD double GainGivenWeight(double g, double h, double w,
                               const SplitParams& p) {
+  if (kSeq) return -(2.0 * g * w + (h + p.lam) * w * w);
   return -(2.0 * g * w + (h + p.lam) * (w * w));
 }
 
@@ -60,6 +68,7 @@ GBT_HD double GainGivenWeight(double g, double h, double w,
 // validity test and the gain expression.  Every single-target evaluator
 // calls this, so all evaluate the same fp64 expression tree and their
 // results are bit-identical.
+template <bool kSeq = false>
 GBT_HD void TryCandidate(long long glq, long long hlq, long long pg,
                          long long ph, double inv_g, double inv_h,
                          const SplitParams& p, int mono, double parent_gain,
@@ -80,8 +89,8 @@ GBT_HD void TryCandidate(long long glq, long long hlq, long long pg,
   if (mono > 0) ok = ok && (wl <= wr);
   if (mono < 0) ok = ok && (wl >= wr);
   if (ok) {
-    const double gain = GainGivenWeight(gl, hl, wl, p)
-                        + GainGivenWeight(gr, hr, wr, p) - parent_gain;
+    const double gain = GainGivenWeight<kSeq>(gl, hl, wl, p)
+                        + GainGivenWeight<kSeq>(gr, hr, wr, p) - parent_gain;
     Best cand{gain, b, dir, glq, hlq};
     if (std::isfinite(gain) && Better(cand, *best)) *best = cand;
   }
