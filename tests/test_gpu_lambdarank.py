@@ -1,20 +1,13 @@
 """LambdaMART HIP kernel (ops/cpp/lambdarank.hip) against the torch path
-on CPU tensors, which tests/test_ranking.py pins to the per-pair oracle.
-
-Tolerance: both sides accumulate in fp64 and cast once to fp32 (2^-24
-relative each); fp64 reordering noise at these sizes is below 1e-9 of the
-largest entry.  Anything larger is a wrong pair, not rounding."""
-import functools
-
+on CPU tensors; reference and tolerance in tests/rank_cases.py."""
 import numpy as np
 import pytest
 import torch
 
-from xgboost_amd.backend.gpu import (LAMBDARANK_MAX_GROUP,
-                                     lambdarank_gpair_gpu,
-                                     lambdarank_schedule)
-from xgboost_amd.data import MetaInfo
+from xgboost_amd.backend.gpu import LAMBDARANK_MAX_GROUP, lambdarank_schedule
 from xgboost_amd.objectives import create_objective
+
+from rank_cases import RankCases, _close
 
 # empty group, singleton, both sides of k = 32, of the wave (64) and of the
 # mid tier (256), and one group several block strides long
@@ -32,51 +25,9 @@ CONFIGS = {
 CASES = [(o, c) for o in OBJECTIVES for c in CONFIGS
          if c != "linear_gain" or o == "rank:ndcg"]
 
-
-def _info(layout, binary, weights=None, seed=0):
-    rng = np.random.RandomState(seed)
-    info = MetaInfo()
-    info.num_row = int(sum(layout))
-    info.group_ptr = np.concatenate([[0], np.cumsum(layout)]).astype(np.int64)
-    y = rng.randint(0, 2 if binary else 5, info.num_row)
-    if binary and len(layout) > 3:
-        y[info.group_ptr[3]:info.group_ptr[4]] = 0  # a group with no hit
-    info.labels = y.astype(np.float32)
-    if weights is not None:
-        info.weights = np.asarray(weights, np.float32)
-    return info
-
-
-@functools.lru_cache(maxsize=None)
-def _case(obj_name, cfg, ties=False):
-    """(info, scores, objective params, CPU reference g and h)."""
-    w = (np.random.RandomState(5).uniform(0.5, 2.0, len(LAYOUT))
-         if cfg == "group_weights" else None)
-    info = _info(LAYOUT, obj_name == "rank:map", w)
-    p = np.random.RandomState(1).randn(info.num_row).round(1)
-    p = np.full_like(p, 0.5) if ties else p
-    p = torch.tensor(p, dtype=torch.float32).view(-1, 1)
-    g, h = create_objective(obj_name, CONFIGS[cfg]).get_gradient(p, info, 0)
-    return info, p, CONFIGS[cfg], g, h
-
-
-def _close(got, ref):
-    got, ref = got.detach().cpu().double(), ref.double()
-    assert got.shape == ref.shape
-    bound = 2.0 ** -22 * ref.abs() + 1e-9 * ref.abs().max()
-    err = (got - ref).abs()
-    assert bool((err <= bound).all()), (
-        f"max err {float(err.max()):.3e} at {int(err.argmax())}, "
-        f"bound there {float(bound.view(-1)[err.argmax()]):.3e}")
-
-
-def _kernel(obj_name, params, info, p):
-    obj = create_objective(obj_name, params)
-    scores = p.cuda().view(-1)
-    state = obj._hip_state(scores, info)
-    assert state is not None
-    return lambdarank_gpair_gpu(scores, state, obj._hip_metric, obj._k(),
-                                obj.score_norm, obj.normalize, obj.exp_gain)
+# binary labels leave group 3 without a hit
+_cases = RankCases(LAYOUT, CONFIGS, no_hit=3, slab=False)
+_info, _case, _kernel = _cases._info, _cases._case, _cases._kernel
 
 
 @pytest.mark.gpu

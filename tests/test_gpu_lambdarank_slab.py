@@ -1,23 +1,18 @@
 """LambdaMART slab tier (ops/cpp/lambdarank_slab.hip, groups above 2048
-documents) against the torch path on CPU tensors, which
-tests/test_ranking.py pins to the per-pair oracle.
-
-Tolerance: both sides accumulate in fp64 and cast once to fp32 (2^-24
-relative each); fp64 reordering noise at these sizes is below 1e-9 of the
-largest entry.  Anything larger is a wrong pair, not rounding."""
-import functools
-
+documents) against the torch path on CPU tensors; reference and tolerance
+in tests/rank_cases.py."""
 import numpy as np
 import pytest
 import torch
 
 from xgboost_amd.backend.gpu import (LAMBDARANK_LDS_MAX_GROUP,
                                      LAMBDARANK_MAX_GROUP, LAMBDARANK_SLAB,
-                                     LAMBDARANK_SLAB_ROWS,
+                                     LAMBDARANK_SLAB_ROWS, LambdaRankState,
                                      lambdarank_gpair_gpu,
                                      lambdarank_schedule)
-from xgboost_amd.data import MetaInfo
 from xgboost_amd.objectives import create_objective
+
+from rank_cases import RankCases, _close
 
 SLAB = LAMBDARANK_SLAB[0]
 # one past the LDS capacity, whole slabs and a few, empty, one wave twice:
@@ -35,52 +30,10 @@ CONFIGS = {
     "group_weights": {},
 }
 
-
-def _info(layout, binary, weights=None):
-    rng = np.random.RandomState(0)
-    info = MetaInfo()
-    info.num_row = int(sum(layout))
-    info.group_ptr = np.concatenate([[0], np.cumsum(layout)]).astype(np.int64)
-    y = rng.randint(0, 2 if binary else 5, info.num_row)
-    if binary:
-        y[:layout[0]] = 0  # a long group with no hit
-    info.labels = y.astype(np.float32)
-    if weights is not None:
-        info.weights = np.asarray(weights, np.float32)
-    return info
-
-
-@functools.lru_cache(maxsize=None)
-def _case(obj_name, cfg, ties=False):
-    """(info, scores, objective params, CPU reference g and h)."""
-    w = (np.random.RandomState(5).uniform(0.5, 2.0, len(LAYOUT))
-         if cfg == "group_weights" else None)
-    info = _info(LAYOUT, obj_name == "rank:map", w)
-    # one decimal: about 70 distinct scores, so ties cross every slab edge
-    p = np.random.RandomState(1).randn(info.num_row).round(1)
-    p = np.full_like(p, 0.5) if ties else p
-    p = torch.tensor(p, dtype=torch.float32).view(-1, 1)
-    g, h = create_objective(obj_name, CONFIGS[cfg]).get_gradient(p, info, 0)
-    return info, p, CONFIGS[cfg], g, h
-
-
-def _close(got, ref):
-    got, ref = got.detach().cpu().double(), ref.double()
-    assert got.shape == ref.shape
-    bound = 2.0 ** -22 * ref.abs() + 1e-9 * ref.abs().max()
-    err = (got - ref).abs()
-    assert bool((err <= bound).all()), (
-        f"max err {float(err.max()):.3e} at {int(err.argmax())}, "
-        f"bound there {float(bound.view(-1)[err.argmax()]):.3e}")
-
-
-def _kernel(obj_name, params, info, p):
-    obj = create_objective(obj_name, params)
-    scores = p.cuda().view(-1)
-    state = obj._hip_state(scores, info)
-    assert state is not None and state.slab is not None
-    return lambdarank_gpair_gpu(scores, state, obj._hip_metric, obj._k(),
-                                obj.score_norm, obj.normalize, obj.exp_gain)
+# binary labels leave the first long group without a hit; every kernel
+# call must have slab work
+_cases = RankCases(LAYOUT, CONFIGS, no_hit=0, slab=True)
+_info, _case, _kernel = _cases._info, _cases._case, _cases._kernel
 
 
 @pytest.mark.gpu
@@ -122,6 +75,41 @@ def test_dispatch_through_objective():
     assert g.is_cuda and g.dtype == torch.float32
     _close(g, rg)
     _close(h, rh)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [32, 300])
+@pytest.mark.parametrize("obj_name", OBJECTIVES)
+def test_slab_agrees_with_lds_tier(obj_name, k):
+    """One group of 600 documents through the LDS "large" tier and, with a
+    slab entry written by hand (three items of 256; k = 300 puts head rows
+    in the second), through the slab kernels, which take any group of at
+    least one document.  The tiers add the row shares in different orders,
+    so the bound is the file's, not equality."""
+    n, kk = 600, min(k, 600)
+    info = _info([n], obj_name == "rank:map", no_hit=False)
+    obj = create_objective(obj_name, {"lambdarank_num_pair_per_sample": k})
+    scores = torch.tensor(np.random.RandomState(1).randn(n).round(1),
+                          dtype=torch.float32).cuda()
+    lds = obj._hip_state(scores, info)
+    assert list(lds.work) == ["large"] and lds.slab is None
+    args = (obj._hip_metric, k, obj.score_norm, obj.normalize, obj.exp_gain)
+    rg, rh = lambdarank_gpair_gpu(scores, lds, *args)
+
+    inv_idcg = None if lds.inv_idcg is None else lds.inv_idcg.cpu().numpy()
+    st = LambdaRankState(info.labels, info.group_ptr, None, scores.device,
+                         inv_idcg, k)
+    st.work = {}
+    st.slab = {
+        "items": torch.tensor([[0, 0], [0, SLAB], [0, 2 * SLAB]],
+                              dtype=torch.int32).cuda(),
+        "item_off": torch.tensor([0, 3], dtype=torch.int32).cuda(),
+        "doc_off": torch.tensor([0, n], dtype=torch.int64).cuda(),
+        "row_off": torch.tensor([0, 3 * kk], dtype=torch.int64).cuda()}
+    st.slab_docs, st.slab_rows = n, 3 * kk
+    g, h = lambdarank_gpair_gpu(scores, st, *args)
+    _close(g, rg.cpu())
+    _close(h, rh.cpu())
 
 
 def test_schedule_slab_entry():

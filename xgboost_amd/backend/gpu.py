@@ -1906,6 +1906,31 @@ LAMBDARANK_SLAB_ROWS = 1 << 23
 LAMBDARANK_DEFAULT_K = 32
 
 
+def _rank_group_counts(group_ptr) -> Tuple[np.ndarray, int, bool]:
+    """Documents per group, the largest count, and whether the pointer
+    starts at 0 with no negative count."""
+    gp = np.asarray(group_ptr, np.int64).reshape(-1)
+    cnt = np.diff(gp)
+    valid = bool(gp.size >= 1 and gp[0] == 0 and (cnt >= 0).all())
+    return cnt, int(cnt.max()) if cnt.size else 0, valid
+
+
+def _rank_slab_items(cnt: np.ndarray, big: np.ndarray,
+                     slab: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The work items of the groups marked in `big`: items per group (0 for
+    the others) and one int32 (group, slab start) row per `slab` documents,
+    largest groups first (ties keep group order), a group's slabs in
+    order."""
+    n_items = np.where(big, -(-cnt // slab), 0)
+    ids = np.nonzero(big)[0]
+    ids = ids[np.argsort(-cnt[ids], kind="stable")]
+    reps = n_items[ids]
+    first = np.cumsum(reps) - reps  # index of each group's first item
+    item_start = (np.arange(int(reps.sum())) - np.repeat(first, reps)) * slab
+    return n_items, np.stack([np.repeat(ids, reps), item_start],
+                             1).astype(np.int32)
+
+
 def lambdarank_schedule(group_ptr: np.ndarray, k: int = LAMBDARANK_DEFAULT_K,
                         slab: int = LAMBDARANK_SLAB[0]) -> dict:
     """Work lists for the ranking kernels, plain numpy.  `lists`: every
@@ -1919,11 +1944,8 @@ def lambdarank_schedule(group_ptr: np.ndarray, k: int = LAMBDARANK_DEFAULT_K,
     items * min(k, n) of them per group.  `eligible` is False when a group
     exceeds LAMBDARANK_MAX_GROUP, the row shares exceed
     LAMBDARANK_SLAB_ROWS or the pointer does not cover [0, N) in order."""
-    gp = np.asarray(group_ptr, np.int64).reshape(-1)
-    cnt = np.diff(gp)
-    max_group = int(cnt.max()) if cnt.size else 0
-    ok = bool(gp.size >= 1 and gp[0] == 0 and (cnt >= 0).all()
-              and max_group <= LAMBDARANK_MAX_GROUP)
+    cnt, max_group, ok = _rank_group_counts(group_ptr)
+    ok = ok and max_group <= LAMBDARANK_MAX_GROUP
     lists = {}
     lo = 0
     for name, (cap, _) in LAMBDARANK_TIERS.items():
@@ -1932,20 +1954,14 @@ def lambdarank_schedule(group_ptr: np.ndarray, k: int = LAMBDARANK_DEFAULT_K,
         lists[name] = ids.astype(np.int32)
         lo = cap
     big = cnt > LAMBDARANK_LDS_MAX_GROUP
-    n_items = np.where(big, -(-cnt // slab), 0)
-    ids = np.nonzero(big)[0]
-    ids = ids[np.argsort(-cnt[ids], kind="stable")]
-    reps = n_items[ids]
-    first = np.cumsum(reps) - reps  # index of each group's first item
-    item_start = (np.arange(int(reps.sum())) - np.repeat(first, reps)) * slab
+    n_items, items = _rank_slab_items(cnt, big, slab)
     rows = n_items * np.minimum(cnt, max(int(k), 0))
 
     def offsets(v):
         return np.concatenate([[0], np.cumsum(v)]).astype(np.int64)
 
     slab_entry = {
-        "items": np.stack([np.repeat(ids, reps), item_start],
-                          1).astype(np.int32),
+        "items": items,
         "item_off": offsets(n_items).astype(np.int32),
         "doc_off": offsets(np.where(big, cnt, 0)),
         "row_off": offsets(rows)}
@@ -2111,23 +2127,13 @@ def rank_metric_schedule(group_ptr: np.ndarray,
     per work item; empty groups have none.  `eligible` is False when a
     group exceeds RANK_METRIC_MAX_GROUP or the pointer is not an ordered
     cover starting at 0."""
-    gp = np.asarray(group_ptr, np.int64).reshape(-1)
-    cnt = np.diff(gp)
-    wave_cap = RANK_METRIC_TIERS["wave"][0]
-    max_group = int(cnt.max()) if cnt.size else 0
-    ok = bool(gp.size >= 1 and gp[0] == 0 and (cnt >= 0).all()
-              and max_group <= RANK_METRIC_MAX_GROUP)
-    big = cnt > wave_cap
-    n_items = np.where(big, -(-cnt // slab), (cnt > 0).astype(np.int64))
-    part_off = np.concatenate([[0], np.cumsum(n_items)])
-    ids = np.nonzero(big)[0]
-    ids = ids[np.argsort(-cnt[ids], kind="stable")]
-    reps = n_items[ids]
-    first = np.cumsum(reps) - reps  # index of each group's first item
-    item_group = np.repeat(ids, reps)
-    item_start = (np.arange(int(reps.sum())) - np.repeat(first, reps)) * slab
-    return {"wave": np.nonzero((cnt > 0) & ~big)[0].astype(np.int32),
-            "block": np.stack([item_group, item_start], 1).astype(np.int32),
+    cnt, max_group, ok = _rank_group_counts(group_ptr)
+    ok = ok and max_group <= RANK_METRIC_MAX_GROUP
+    big = cnt > RANK_METRIC_TIERS["wave"][0]
+    wave = (cnt > 0) & ~big  # one item each
+    n_items, items = _rank_slab_items(cnt, big, slab)
+    part_off = np.concatenate([[0], np.cumsum(n_items + wave)])
+    return {"wave": np.nonzero(wave)[0].astype(np.int32), "block": items,
             "part_off": part_off.astype(np.int32), "max_group": max_group,
             "eligible": ok and int(part_off[-1]) < 2 ** 31}
 

@@ -4,7 +4,9 @@
 //
 // Specification: _LambdaRankBase.get_gradient (objectives.py), top-k pair
 // method, which follows the reference's LambdaGrad / MakePairs
-// (src/objective/lambdarank_obj.h).  The reference's device path is one
+// (src/objective/lambdarank_obj.h); the pair gradient, the rank key, the
+// statistics' terms, the normaliser and the final write are rank_common.h's,
+// shared with the slab tier.  The reference's device path is one
 // thread per pair with global atomics; fp64 atomics CAS-loop here and the
 // head documents are ~n-way contended, so this kernel has no atomics:
 //
@@ -14,8 +16,8 @@
 //             asc) -- unique keys, so the ranks are a permutation and
 //             equal scores come out in document order -- then scatter
 //             score, label, doc index to their rank slot
-//  3. stats   ndcg: discount 1/log2(r+2) and gain per rank; map: fp64
-//             block scan of n_rel and acc = cumsum(y/(r+1)) down the list
+//  3. stats   ndcg: discount and gain per rank; map: fp64 block scan of
+//             n_rel and acc = cumsum(y/(r+1)) down the list
 //  4. pairs   rows i < min(k, n); each thread owns the columns
 //             j = t, t + T, ... and keeps their g/h sums in registers.
 //             Pair (i, j) is evaluated once: the column share goes to the
@@ -23,22 +25,20 @@
 //             with a shuffle butterfly and parked in part[i][wave].  One
 //             barrier per kRowChunk rows (one in all for k <= 64), then
 //             the owner of column i folds part[i][*] in wave order.
-//  5. write   group normaliser, weight, hessian floor, fp32 cast, store
-//             through the rank -> document map.
+//  5. write   StoreGpair through the rank -> document map.
 //
 // Every sum has a fixed order, so a tier's output is bit-reproducible.
 // Tiers: groups of <= 64 documents take one wave each (four per block,
 // no block barrier anywhere); larger groups take one block each.
 #include "gbt_kernels.h"
+#include "rank_common.h"
 
 #include <hip/hip_runtime.h>
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kRowChunk = 64;  // rows between two barriers of the pair loop
-
-enum : int { kNdcg = 0, kMap = 1, kPairwise = 2 };
+constexpr int kPairwise = 2;
 
 struct LambdaRankArgs {
   const float* scores;
@@ -75,35 +75,6 @@ struct GroupLds {
   double scan_c[kWaves];
   double scan_a[kWaves];
 };
-
-// Barrier over the threads that share one group: the block, or for the
-// one-wave tier only the wave (waves of a block run different groups of
-// different sizes there, so a block barrier would be wrong as well as
-// slow).
-template <int kWaves>
-__device__ inline void GroupSync() {
-  if constexpr (kWaves > 1) {
-    __syncthreads();
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-}
-
-__device__ inline double WaveSum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
-// ascending float order -> descending unsigned order (-0 was folded into
-// +0 by the caller, so equal floats have equal keys)
-__device__ inline unsigned int DescKey(float s) {
-  const unsigned int u = __float_as_uint(s);
-  const unsigned int asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~asc;
-}
 
 template <int kMetric, int kCap, int kThreads, int kGroups>
 __global__ __launch_bounds__(kThreads* kGroups) void LambdaRankKernel(
@@ -142,7 +113,7 @@ __global__ __launch_bounds__(kThreads* kGroups) void LambdaRankKernel(
       my_y[m] = a.labels[base + d];
       const unsigned int key = DescKey(my_s[m]);
       s.key[d] = key;
-      my_key[m] = ((unsigned long long)key << 32) | (unsigned int)d;
+      my_key[m] = RankKey(key, d);
     }
   }
   GroupSync<kWaves>();
@@ -152,8 +123,7 @@ __global__ __launch_bounds__(kThreads* kGroups) void LambdaRankKernel(
 #pragma unroll
   for (int m = 0; m < kPer; ++m) rank[m] = 0;
   for (int e = 0; e < n; ++e) {
-    const unsigned long long ke =
-        ((unsigned long long)s.key[e] << 32) | (unsigned int)e;
+    const unsigned long long ke = RankKey(s.key[e], e);
 #pragma unroll
     for (int m = 0; m < kPer; ++m) rank[m] += ke < my_key[m] ? 1 : 0;
   }
@@ -175,9 +145,8 @@ __global__ __launch_bounds__(kThreads* kGroups) void LambdaRankKernel(
     for (int m = 0; m < kPer; ++m) {
       const int r = t + m * kThreads;
       if (r < n) {
-        const double y = (double)s.label[r];
-        s.st0[r] = 1.0 / log2((double)(r + 2));
-        s.st1[r] = a.exp_gain ? exp2(y) - 1.0 : y;
+        s.st0[r] = NdcgDiscount(r);
+        s.st1[r] = NdcgGain((double)s.label[r], a.exp_gain);
       }
     }
     inv_idcg = a.inv_idcg[gidx];
@@ -194,22 +163,8 @@ __global__ __launch_bounds__(kThreads* kGroups) void LambdaRankKernel(
         ac += y / (double)(e + 1);
       }
     }
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      const double tc = __shfl_up(c, off, kWave);
-      const double ta = __shfl_up(ac, off, kWave);
-      if (lane >= off) {
-        c += tc;
-        ac += ta;
-      }
-    }
-    // exclusive prefix of this thread's chunk
-    double run_c = __shfl_up(c, 1, kWave);
-    double run_a = __shfl_up(ac, 1, kWave);
-    if (lane == 0) {
-      run_c = 0.0;
-      run_a = 0.0;
-    }
+    double run_c, run_a;  // exclusive prefix of this thread's chunk
+    MapWaveScan(lane, c, ac, run_c, run_a);
     if constexpr (kWaves > 1) {
       if (lane == kWave - 1) {
         s.scan_c[wave] = c;
@@ -276,30 +231,23 @@ __global__ __launch_bounds__(kThreads* kGroups) void LambdaRankKernel(
           if (j > i && j < n) {
             const float yj = s.label[j];
             if (yj != yi) {
-              const bool swap = yi < yj;  // the lower-ranked doc is better
               const double sj = (double)s.score[j];
-              const double ds = swap ? sj - si : si - sj;  // high - low
-              const double sig = 1.0 / (1.0 + exp(-ds));
-              double delta = 1.0;
-              if constexpr (kMetric == kNdcg) {
-                // (gain_h - gain_l)(disc_h - disc_l): both factors flip
-                // sign together under swap
-                delta = fabs((b_i - s.st1[j]) * (a_i - s.st0[j]) * inv_idcg);
-              } else if constexpr (kMetric == kMap) {
-                // DeltaMAP with positions ordered (i above j)
-                delta = fabs((a_i - s.st0[j] / (double)(j + 1) +
-                              (s.st1[j - 1] - b_i)) / n_total);
-              }
-              if (do_norm) delta = delta / (fabs(ds) + 0.01);
-              const double lam = (sig - 1.0) * delta;
-              const double hess =
-                  fmax(sig * (1.0 - sig), 1e-16) * delta * 2.0;
-              const double va = swap ? -lam : lam;  // gradient at row i
-              acc_g[m] -= va;
-              acc_h[m] += hess;
-              pg += va;
-              ph += hess;
-              s_loc += -2.0 * lam;
+              const auto col = [&s, j](double& a_j, double& b_j) {
+                if constexpr (kMetric == kNdcg) {
+                  b_j = s.st1[j];
+                  a_j = s.st0[j];
+                } else if constexpr (kMetric == kMap) {
+                  a_j = s.st0[j] / (double)(j + 1);
+                  b_j = s.st1[j - 1];  // acc of the rank above
+                }
+              };
+              const PairTerms p = PairGrad<kMetric>(
+                  yi, si, a_i, b_i, yj, sj, col, inv_idcg, n_total, do_norm);
+              acc_g[m] -= p.va;
+              acc_h[m] += p.hess;
+              pg += p.va;
+              ph += p.hess;
+              s_loc += -2.0 * p.lam;
             }
           }
         }
@@ -351,22 +299,14 @@ __global__ __launch_bounds__(kThreads* kGroups) void LambdaRankKernel(
     } else {
       for (int w = 0; w < kWaves; ++w) sum += s.wsum[w];
     }
-    if (sum > 0.0) norm = log2(1.0 + sum) / sum;
+    norm = GroupNorm(sum);
   }
 #pragma unroll
   for (int m = 0; m < kPer; ++m) {
     const int j = t + m * kThreads;
     if (j < n) {
-      const long long d = base + s.doc[j];
-      double g = acc_g[m] * norm;
-      double h = acc_h[m] * norm;
-      if (a.weight != nullptr) {
-        const double w = a.weight[d];
-        g *= w;
-        h *= w;
-      }
-      a.out_g[d] = (float)g;
-      a.out_h[d] = (float)fmax(h, 1e-16);
+      StoreGpair(a.out_g, a.out_h, base + s.doc[j], acc_g[m], acc_h[m], norm,
+                 a.weight);
     }
   }
 }

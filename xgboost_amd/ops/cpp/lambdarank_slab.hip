@@ -2,10 +2,9 @@
 // tiers (above 2048 documents): the slab tier.
 //
 // Specification: the same as lambdarank.hip, _LambdaRankBase.get_gradient
-// (objectives.py), top-k pair method: rank order (score descending,
-// document ascending), ndcg / map / pairwise delta, the degenerate-group
-// rule for the score normalisation, the log2(1 + s) / s group normaliser,
-// the per-document weight, the 1e-16 hessian floor, one fp64 -> fp32 cast.
+// (objectives.py), top-k pair method, through the same definitions
+// (rank_common.h): rank key, statistics' terms, pair gradient, group
+// normaliser and final write.
 //
 // A work item is one slab of one group: kThreads * kPer consecutive
 // positions (documents in launch 1, ranks afterwards) that the threads of
@@ -43,8 +42,8 @@
 //  4. finish   one block per slab: s_part of the group in slab order and
 //              the normaliser; for each owned rank the column sum, plus
 //              for a head rank the row shares of the items that have a
-//              column above it, in slab order; normaliser, weight, hessian
-//              floor, fp32 cast, store through the rank -> document map.
+//              column above it, in slab order; StoreGpair through the
+//              rank -> document map.
 //
 // No atomics and every sum in a fixed order: the output is
 // bit-reproducible.  Every scratch entry that is read has been written by
@@ -55,18 +54,17 @@
 // documents: the most blocks for a lone long group and the fewest
 // registers in the pair kernel (profiles/lambdarank_mi355x.md).
 #include "gbt_kernels.h"
+#include "rank_common.h"
 
 #include <hip/hip_runtime.h>
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kRowChunk = 64;  // head rows in LDS at a time
 constexpr int kTile = 2048;    // score keys per LDS tile of the rank pass
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
-
-enum : int { kNdcg = 0, kMap = 1, kPairwise = 2 };
+constexpr int kPairwise = 2;
 
 struct SlabArgs {
   const float* scores;
@@ -98,20 +96,6 @@ struct SlabArgs {
   float* out_h;
 };
 
-__device__ inline double WaveSum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
-// ascending float order -> descending unsigned order (-0 was folded into
-// +0 by the caller, so equal floats have equal keys)
-__device__ inline unsigned int DescKey(float s) {
-  const unsigned int u = __float_as_uint(s);
-  const unsigned int asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~asc;
-}
-
 struct Item {
   int gidx, start, n;
   long long base;
@@ -141,8 +125,7 @@ __device__ __forceinline__ void CountTile(const unsigned int* tile, int t0,
   static_assert(kAct <= kPer, "active documents");
 #pragma unroll 4
   for (int j = 0; j < len; ++j) {
-    const unsigned long long ke =
-        ((unsigned long long)tile[j] << 32) | (unsigned int)(t0 + j);
+    const unsigned long long ke = RankKey(tile[j], t0 + j);
 #pragma unroll
     for (int m = 0; m < kAct; ++m) rank[m] += ke < key[m] ? 1 : 0;
   }
@@ -169,8 +152,7 @@ __global__ __launch_bounds__(kThreads) void SlabRankKernel(const SlabArgs a) {
     rank[m] = 0;
     if (d < n) {
       my_s[m] = a.scores[it.base + d] + 0.0f;
-      my_key[m] =
-          ((unsigned long long)DescKey(my_s[m]) << 32) | (unsigned int)d;
+      my_key[m] = RankKey(DescKey(my_s[m]), d);
     }
   }
   const int owned = n - it.start < kSlab ? n - it.start : kSlab;
@@ -180,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void SlabRankKernel(const SlabArgs a) {
     const int len = n - t0 < kTile ? n - t0 : kTile;
     if (t0 > 0) __syncthreads();  // the last tile has been read
     for (int j = t; j < len; j += kThreads) {
-      tile[j] = DescKey(a.scores[it.base + t0 + j] + 0.0f);
+      tile[j] = DescKey(a.scores[it.base + t0 + j]);
     }
     __syncthreads();
     if (kPer >= 8 && act > 4) {
@@ -233,21 +215,8 @@ __global__ __launch_bounds__(kThreads) void SlabMapScanKernel(const SlabArgs a) 
       c += y[q];
       ac += y[q] / (double)(e + 1);
     }
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const double tc = __shfl_up(c, o, kWave);
-      const double ta = __shfl_up(ac, o, kWave);
-      if (lane >= o) {
-        c += tc;
-        ac += ta;
-      }
-    }
-    double run_c = __shfl_up(c, 1, kWave);
-    double run_a = __shfl_up(ac, 1, kWave);
-    if (lane == 0) {
-      run_c = 0.0;
-      run_a = 0.0;
-    }
+    double run_c, run_a;
+    MapWaveScan(lane, c, ac, run_c, run_a);
     if (t0 > 0) __syncthreads();  // the last span's totals have been read
     if (lane == kWave - 1) {
       scan_c[wave] = c;
@@ -323,9 +292,8 @@ __global__ __launch_bounds__(kThreads) void SlabPairsKernel(const SlabArgs a) {
       col_y[m] = ry[j];
       col_s[m] = (double)rs[j];
       if constexpr (kMetric == kNdcg) {
-        const double y = (double)col_y[m];
-        col_a[m] = 1.0 / log2((double)(j + 2));
-        col_b[m] = a.exp_gain ? exp2(y) - 1.0 : y;
+        col_a[m] = NdcgDiscount(j);
+        col_b[m] = NdcgGain((double)col_y[m], a.exp_gain);
       } else if constexpr (kMetric == kMap) {
         col_a[m] = st0[j] / (double)(j + 1);
         col_b[m] = j > 0 ? st1[j - 1] : 0.0;
@@ -344,8 +312,8 @@ __global__ __launch_bounds__(kThreads) void SlabPairsKernel(const SlabArgs a) {
       row_s[t] = rs[i];
       row_y[t] = y;
       if constexpr (kMetric == kNdcg) {
-        row_a[t] = 1.0 / log2((double)(i + 2));
-        row_b[t] = a.exp_gain ? exp2((double)y) - 1.0 : (double)y;
+        row_a[t] = NdcgDiscount(i);
+        row_b[t] = NdcgGain((double)y, a.exp_gain);
       } else if constexpr (kMetric == kMap) {
         row_a[t] = st0[i] / (double)(i + 1);
         row_b[t] = st1[i];
@@ -365,27 +333,18 @@ __global__ __launch_bounds__(kThreads) void SlabPairsKernel(const SlabArgs a) {
       for (int m = 0; m < kPer; ++m) {
         const int j = it.start + t + m * kThreads;
         if (j > i && j < n && col_y[m] != yi) {
-          const bool swap = yi < col_y[m];  // the lower-ranked doc is better
-          const double ds = swap ? col_s[m] - si : si - col_s[m];
-          const double sig = 1.0 / (1.0 + exp(-ds));
-          double delta = 1.0;
-          if constexpr (kMetric == kNdcg) {
-            // (gain_h - gain_l)(disc_h - disc_l): both factors flip sign
-            // together under swap
-            delta = fabs((b_i - col_b[m]) * (a_i - col_a[m]) * inv_idcg);
-          } else if constexpr (kMetric == kMap) {
-            // DeltaMAP with positions ordered (i above j)
-            delta = fabs((a_i - col_a[m] + (col_b[m] - b_i)) / n_total);
-          }
-          if (do_norm) delta = delta / (fabs(ds) + 0.01);
-          const double lam = (sig - 1.0) * delta;
-          const double hess = fmax(sig * (1.0 - sig), 1e-16) * delta * 2.0;
-          const double va = swap ? -lam : lam;  // gradient at row i
-          acc_g[m] -= va;
-          acc_h[m] += hess;
-          pg += va;
-          ph += hess;
-          s_loc += -2.0 * lam;
+          const auto col = [&](double& a_j, double& b_j) {
+            a_j = col_a[m];
+            b_j = col_b[m];
+          };
+          const PairTerms p = PairGrad<kMetric>(yi, si, a_i, b_i, col_y[m],
+                                                col_s[m], col, inv_idcg,
+                                                n_total, do_norm);
+          acc_g[m] -= p.va;
+          acc_h[m] += p.hess;
+          pg += p.va;
+          ph += p.hess;
+          s_loc += -2.0 * p.lam;
         }
       }
       pg = WaveSum(pg);
@@ -445,7 +404,7 @@ __global__ __launch_bounds__(kThreads) void SlabFinishKernel(const SlabArgs a) {
   if (a.normalize) {
     double sum = 0.0;
     for (int s = 0; s < n_slabs; ++s) sum += a.s_part[first + s];
-    if (sum > 0.0) norm = log2(1.0 + sum) / sum;
+    norm = GroupNorm(sum);
   }
 #pragma unroll
   for (int m = 0; m < kPer; ++m) {
@@ -463,18 +422,9 @@ __global__ __launch_bounds__(kThreads) void SlabFinishKernel(const SlabArgs a) {
           }
         }
       }
-      g *= norm;
-      h *= norm;
       const int doc = a.r_doc[off + j];
       if (doc < 0 || doc >= n) continue;  // never: the ranks are a permutation
-      const long long d = it.base + doc;
-      if (a.weight != nullptr) {
-        const double w = a.weight[d];
-        g *= w;
-        h *= w;
-      }
-      a.out_g[d] = (float)g;
-      a.out_h[d] = (float)fmax(h, 1e-16);
+      StoreGpair(a.out_g, a.out_h, it.base + doc, g, h, norm, a.weight);
     }
   }
 }

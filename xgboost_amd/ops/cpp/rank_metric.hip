@@ -34,14 +34,13 @@
 // Tiers: groups of <= 64 documents take one wave each, four per block, no
 // block barrier; every other group takes one block per slab.
 #include "gbt_kernels.h"
+#include "rank_common.h"
 
 #include <hip/hip_runtime.h>
 
 namespace {
 
-constexpr int kWave = 64;
-
-enum : int { kNdcg = 0, kMap = 1, kPre = 2 };
+constexpr int kPre = 2;
 
 struct RankMetricArgs {
   const float* scores;
@@ -54,33 +53,10 @@ struct RankMetricArgs {
   double* partial;
 };
 
-// Barrier over the threads that share one work item: the block, or for the
-// one-wave tier only the wave (the waves of a block run different groups).
-template <int kWaves>
-__device__ inline void ItemSync() {
-  if constexpr (kWaves > 1) {
-    __syncthreads();
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-}
-
-__device__ inline double WaveSum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
-// Ascending float order -> descending unsigned order.  -0 folds into +0, so
-// equal floats have equal keys; NaN takes the last key, where a stable
-// descending argsort puts it.
-__device__ inline unsigned int DescKey(float s) {
+// NaN takes the last key, where a stable descending argsort puts it
+__device__ inline unsigned int NanLastKey(float s) {
   if (s != s) return 0xFFFFFFFFu;
-  const unsigned int u = __float_as_uint(s + 0.0f);
-  const unsigned int asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~asc;
+  return DescKey(s);
 }
 
 template <int kKind>
@@ -88,7 +64,7 @@ __device__ inline unsigned long long DocKey(const RankMetricArgs& a,
                                             long long base, int d) {
   unsigned int lo = (unsigned int)d << 1;
   if constexpr (kKind == kMap) lo |= a.labels[base + d] > 0.0f ? 1u : 0u;
-  return ((unsigned long long)DescKey(a.scores[base + d]) << 32) | lo;
+  return RankKey(NanLastKey(a.scores[base + d]), lo);
 }
 
 // One pass of `len` staged keys over the first kAct owned documents.
@@ -160,11 +136,11 @@ __global__ __launch_bounds__(kThreads* kGroups) void RankMetricKernel(
   // ---- stream the group's keys through the tile ------------------------------
   for (int t0 = 0; t0 < n; t0 += kTile) {
     const int len = n - t0 < kTile ? n - t0 : kTile;
-    if (t0 > 0) ItemSync<kWaves>();  // the last tile has been read
+    if (t0 > 0) GroupSync<kWaves>();  // the last tile has been read
     for (int j = t; j < len; j += kThreads) {
       tile[j] = DocKey<kKind>(a, base, t0 + j);
     }
-    ItemSync<kWaves>();
+    GroupSync<kWaves>();
     if (kPer >= 8 && act > 4) {
       CountTile<kKind, kPer >= 8 ? 8 : kPer>(tile, len, my_key, rank, hits);
     } else if (kPer >= 4 && act > 2) {
@@ -185,7 +161,8 @@ __global__ __launch_bounds__(kThreads* kGroups) void RankMetricKernel(
     if (d < n && rank[m] < kk) {
       const double y = (double)a.labels[base + d];
       if constexpr (kKind == kNdcg) {
-        sum += (exp2(y) - 1.0) / log2((double)(rank[m] + 2));
+        // a division, not NdcgDiscount's reciprocal: metrics.ndcg divides
+        sum += NdcgGain(y, true) / log2((double)(rank[m] + 2));
       } else if constexpr (kKind == kMap) {
         if (y > 0.0) sum += (double)hits[m] / (double)(rank[m] + 1);
       } else {
